@@ -12,9 +12,16 @@ the metric ("10M x 1k mixed") is quoted on.  With N > 1 every rank owns its own 
 
 Rank 0 prints ONE JSON line.  value = algorithmic bytes of the whole job (every operand read
 once, result written once) / wall time of a step, in GB/s; gflops is reported
-next to it.  `roofline` describes the dominant kernel, timed live with HIP events on the
-launch stream (tm_profile_* in the C ABI); `cpu_baseline` is the CPU oracle ("port") timed on
-this box's host cores on a bounded row sample of the same workload.
+next to it.  A plain run sets up, warms up, times the K steps and prints that line, nothing else.
+
+--full adds every side measurement to the line: `roofline` describes the dominant kernel, timed
+live with HIP events on the launch stream (tm_profile_* in the C ABI); `cpu_baseline` is the CPU
+oracle ("port") timed on the host's cores on a bounded row sample of the same workload;
+the min step, the f64-only and HIP-graph steps, matvec / transpose_matvec and the ingest rebuild.
+
+--dump-outputs DIR writes what the last timed step returned as DIR/sandwich.npy (see
+dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared
+output for output.
 """
 from __future__ import annotations
 
@@ -70,8 +77,13 @@ METRIC = _baseline_metric()
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (roofline, per-kernel breakdown, traffic, CPU "
+                         "baseline, min / f64-only / HIP-graph steps, matvec, ingest rebuild)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result of the last timed step as DIR/<name>.npy")
     ap.add_argument("--rows", type=int, default=10_000_000, help="rows per GPU")
     ap.add_argument("--workload", default="cfg4",
                     choices=["cfg4", "cfg2", "cfg3", "cfg1", "dense", "sparse", "sparse_narrow",
@@ -84,12 +96,17 @@ def parse_args():
     ap.add_argument("--cpu-rows", type=int, default=0,
                     help="rows of the bounded CPU-baseline sample (0 = per-workload default)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--breakdown", action="store_true", help="per-op kernel times to stderr")
-    ap.add_argument("--out", default=None, help="also write the JSON (+breakdown) to this file")
+    ap.add_argument("--breakdown", action="store_true", help="per-op kernel times to stderr (with --full)")
+    ap.add_argument("--out", default=None, help="also write the JSON (+breakdown with --full) to this file")
     ap.add_argument("--no-traffic", action="store_true",
                     help="skip the rocprofv3 FETCH_SIZE / WRITE_SIZE passes over the dominant kernel")
     ap.add_argument("--traffic-child", default=None, help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.breakdown and not args.full:
+        ap.error("--breakdown needs --full")
+    return args
 
 
 def build_workload(name, n, seed):
@@ -386,6 +403,26 @@ def cpu_baseline(workload, rows, mat, d):
     }
 
 
+DUMP_WHOLE_MAX_BYTES = 60 << 20   # the dump stays under 64 MB
+DUMP_SAMPLE_ENTRIES = 4 << 20
+
+
+def dump_outputs(dirname, outputs):
+    """Write each device result of `outputs` ({name: tensor}) as dirname/<name>.npy, float32 or float64 as the caller
+    received it.  A result larger than DUMP_WHOLE_MAX_BYTES (a p x p sandwich past ~2800 columns) is written as a
+    fixed sample: its entries at DUMP_SAMPLE_ENTRIES flat positions drawn by numpy default_rng(0), sorted and
+    de-duplicated -- the same positions for the same shape on every run."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in outputs.items():
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64)
+        if t.numel() * t.element_size() > DUMP_WHOLE_MAX_BYTES:
+            pos = np.unique(np.random.default_rng(0).integers(0, t.numel(), DUMP_SAMPLE_ENTRIES))
+            t = t.reshape(-1)[torch.from_numpy(pos).to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy())
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: start N ranks of this script through
     torch.distributed.run (one process per GPU, rendezvous on 127.0.0.1) and pass rank 0's
@@ -507,7 +544,8 @@ def main():
     ingest = {"ingest_ms": round((time.perf_counter() - t_ing) * 1e3, 1),
               "ingest_peak_bytes": int(torch.cuda.max_memory_allocated()),
               "data_bytes": int(data_bytes), "synth_ms": round(synth_ms, 1)}
-    ingest["ingest_rebuild_ms"] = _rebuild_twins_ms(mat)
+    if args.full:
+        ingest["ingest_rebuild_ms"] = _rebuild_twins_ms(mat)
     n_local, p = mat.shape
     g = torch.Generator(device="cuda")
     g.manual_seed(100 + rank)
@@ -568,21 +606,28 @@ def main():
         rank_ms = [round(float(x) / args.steps * 1e3, 4) for x in mine.tolist()]
         elapsed = float(mine.max().item())
     ms_per_step = elapsed / args.steps * 1e3
-    # min over individually timed steps next to the mean (the reference harness reports the
-    # minimum, benchmark/main.py:108-128); outside the timed region above
-    per_step = []
-    for _ in range(min(args.steps, 10)):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        step()
-        e1.record()
-        e1.synchronize()
-        per_step.append(e0.elapsed_time(e1))
-    ms_min = min(per_step)
+    # before anything else launches: the graph replay returns a static buffer that the next step overwrites
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"sandwich": out})
+
+    # everything below up to the result line is a side measurement of --full
+    ms_min = None
+    if args.full:
+        # min over individually timed steps next to the mean (the reference harness reports the
+        # minimum, benchmark/main.py:108-128); outside the timed region above
+        per_step = []
+        for _ in range(min(args.steps, 10)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            step()
+            e1.record()
+            e1.synchronize()
+            per_step.append(e0.elapsed_time(e1))
+        ms_min = min(per_step)
 
     # what arithmetic the dense self term ran in, and the same step with the int8-sliced syrk switched off
     dense_term, handovers, ms_f64_only = None, None, None
-    if tdt == torch.float64 and not use_graph:
+    if args.full and tdt == torch.float64 and not use_graph:
         dms = [m for m in (mat.matrices if isinstance(mat, tm.SplitMatrix) else [mat])
                if isinstance(m, tm.DenseMatrix)]
         took_i8 = [m for m in dms if getattr(m, "_i8_hist", None)]
@@ -612,7 +657,8 @@ def main():
     # the same launch sequence replayed from a HIP graph (the form a solver's per-iteration product takes,
     # SplitMatrix.sandwich_graph), reported beside the eager step -- never `value`
     ms_graph = None
-    if world == 1 and not use_graph and hasattr(mat, "_sandwich_dev") and not isinstance(mat, tm.CategoricalMatrix):
+    if (args.full and world == 1 and not use_graph and hasattr(mat, "_sandwich_dev")
+            and not isinstance(mat, tm.CategoricalMatrix)):
         from tabmat_amd.graph import CapturedProduct
 
         try:
@@ -633,7 +679,7 @@ def main():
     # times all three products, benchmark/main.py:58-62,108-128): per-GPU sub-records, never `value`.
     # Algorithmic bytes = the blocks once + the input and output vectors.
     mv = {}
-    if True:
+    if args.full:
         blk_bytes = synth.algorithmic_bytes(mat) - n_local * np.dtype(mat.dtype).itemsize - (
             p * p * 8 if isinstance(mat, tm.SplitMatrix) else
             p * np.dtype(mat.dtype).itemsize if isinstance(mat, tm.CategoricalMatrix) else
@@ -674,73 +720,6 @@ def main():
 
     result = None
     if rank == 0:
-        bd = kernel_breakdown(mat, d)
-        dom = max(bd, key=bd.get)
-        dom_ms = bd[dom]
-        dom_bytes = op_algorithmic_bytes(mat, dom)
-        dom_flops = op_flops(mat, dom)
-        hbm_time = dom_bytes / (HBM_PEAK_GBS * 1e9)
-        peak_tf = MFMA_F64_PEAK_TFLOPS if tdt == torch.float64 else MFMA_F32_PEAK_TFLOPS
-        mfma_note = None
-        if (dom_flops and tdt == torch.float32 and isinstance(mat, tm.DenseMatrix) and 128 < p <= 256
-                and p % 4 == 0):
-            # the f32 syrk of 129..256 columns runs as SIX bf16 piece products on the bf16 matrix cores
-            # (csrc/syrk_bf16.hip): priced against the dense bf16 peak with the flops it really issues
-            dom_flops *= 6.0
-            peak_tf = MFMA_BF16_PEAK_TFLOPS
-            mfma_note = ("f32 syrk as 6 bf16 piece products (3-piece split, f32 accumulation): achieved = "
-                         "6 x n k (k + 1) bf16 flop / kernel time, peak = dense bf16 MFMA")
-        mfma_time = (dom_flops / (peak_tf * 1e12)) if dom_flops else 0.0
-        dom_lds = op_lds_bytes(mat, dom)
-        lds_time = (dom_lds / (LDS_PEAK_GBS * 1e9)) if dom_lds else 0.0
-        # the bounding roofline of the dominant kernel ("hbm" | "mfma"): MFMA when its matrix time
-        # exceeds its HBM time, else HBM -- `frac` is against THAT bound.  A kernel whose inner loop is an LDS
-        # gather additionally carries `frac_lds` (its algorithmic LDS bytes against the guide's aggregate LDS
-        # rate): a second opinion on what limits it, never `frac`.
-        if mfma_time > hbm_time:
-            roof = {"bound": "mfma", "achieved": round(dom_flops / (dom_ms * 1e-3) / 1e12, 3),
-                    "peak": peak_tf, "unit": "TFLOP/s"}
-        else:
-            roof = {"bound": "hbm", "achieved": round(dom_bytes / (dom_ms * 1e-3) / 1e9, 1),
-                    "peak": HBM_PEAK_GBS, "unit": "GB/s"}
-        roof["frac"] = round(roof["achieved"] / roof["peak"], 4)
-        # (the same kernel against the HBM roofline, whatever binds it)
-        roof["frac_hbm"] = round(dom_bytes / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-        if dom_lds:
-            roof["frac_lds"] = round(dom_lds / (dom_ms * 1e-3) / 1e9 / LDS_PEAK_GBS, 4)
-            roof["algorithmic_lds_bytes_per_launch"] = int(dom_lds)
-            roof["lds_peak_gbs"] = LDS_PEAK_GBS
-        # HBM bytes per launch of that kernel, measured NOW: rocprofv3 --pmc passes over a child
-        # run that launches the same op (null when rocprofv3 is unavailable or N > 1)
-        roof["traffic"] = None
-        if world == 1 and not args.no_traffic:
-            roof["traffic"] = measure_traffic(args, dom)
-        # the dense self-sandwich: against the matrix spec of its dtype when it ran on that dtype's MFMA; when it
-        # ran in 40-bit fixed point on the INT8 matrix cores (K1e) an f64-equivalent flop rate against the f64
-        # spec would not be a utilisation: it is priced against HBM (it streams the block once) and by the int8
-        # operations it issues (22 digit-pair products of n k (k + 1) / 2 MACs each, padded to 128 columns)
-        mfma_frac, dense_self = None, None
-        i8_ran = bool(dense_term and dense_term.startswith("int8"))
-        for name, ms in bd.items():
-            fl = op_flops(mat, name)
-            if not fl:
-                continue
-            if i8_ran:
-                by = op_algorithmic_bytes(mat, name)
-                kk = [m for m in (mat.matrices if isinstance(mat, tm.SplitMatrix) else [mat])
-                      if isinstance(m, tm.DenseMatrix)][0].shape[1]
-                kp = -(-kk // 128) * 128 if kk <= 128 else kk
-                dense_self = {"kernel": name, "ms": round(ms, 4), "arithmetic": "int8x5 digits, 22 digit pairs, int32 acc",
-                              "frac_hbm": round(by / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                              "int8_tops": round(22.0 * n_local * kp * (kp + 16) / (ms * 1e-3) / 1e12, 1),
-                              "int8_peak_tops_dense": INT8_PEAK_TOPS}
-            else:
-                mfma_frac = round(fl * (6.0 if mfma_note else 1.0) / (ms * 1e-3) / (peak_tf * 1e12), 4)
-        if mfma_note:
-            roof["note"] = mfma_note
-        roof["kernel"] = dom
-        roof["kernel_ms"] = round(dom_ms, 4)
-        roof["algorithmic_bytes_per_launch"] = int(dom_bytes)
         wl_names = {
             "cfg4": f"SplitMatrix.sandwich: dense128 + csr512@5% + cats(256,96,32), {n_local} rows/GPU, p={p}, float64 (BASELINE configs[3])",
             "cfg2": f"DenseMatrix.sandwich float32 {n_local}x256 (BASELINE configs[1])",
@@ -769,60 +748,132 @@ def main():
                        "launch": "hipgraph replay" if use_graph else "eager",
                        "sharding": "rows" if world > 1 else "none",
                        "collective": "all_reduce(p*p f64)" if world > 1 else "none"},
-            "roofline": roof,
-            "ms_per_step_min": round(ms_min, 4),
-            "hbm_frac_whole_job": round(alg_bytes / world / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-            # whole step against max(HBM, MFMA): bytes / 8 TB/s vs flops / dense matrix peak of the dtype
-            "mixed_roofline_ms": round(max(alg_bytes / world / (HBM_PEAK_GBS * 1e9),
-                                           flops * (6.0 if mfma_note else 1.0) / world / (peak_tf * 1e12)) * 1e3, 4),
-            "mfma_frac_of_spec": mfma_frac,
-            "dense_self": dense_self,
-            "sum_kernel_ms": round(sum(bd.values()), 4),
-            "matvec": mv.get("matvec"),
-            "transpose_matvec": mv.get("transpose_matvec"),
-            "dense_term": dense_term,
-            "dense_term_handover": handovers,
-            "ms_per_step_f64_only": None if ms_f64_only is None else round(ms_f64_only, 4),
-            "ms_per_step_hipgraph": None if ms_graph is None else round(ms_graph, 4),
         }
-        if args.workload == "cfg4":
-            scale = n_local / 10_000_000
-            floor = sum(v[0] for v in DESIGN_FLOOR_CFG4_MS.values()) * scale
-            result["design_floor_ms"] = round(floor, 2)
-            result["design_floor"] = {
-                "what": ("per-GPU step time of the CURRENT formulation (one kernel per block product) with every "
-                         "kernel at the floor its own ablation shows; the north star's 0.60 of HBM peak would be "
-                         f"{alg_bytes / world / (0.6 * HBM_PEAK_GBS * 1e9) * 1e3:.2f} ms, below the f64 arithmetic of the "
-                         "dense term at any rate this chip has (SURVEY.md 8d)"),
-                "terms_ms_at_10M_rows": {k: {"ms": v[0], "from": v[1]} for k, v in DESIGN_FLOOR_CFG4_MS.items()},
-                "step_over_floor": round(ms_per_step / floor, 3),
-            }
-        # ingest as a measured quantity: to_device() = every twin the three products stream, built
-        # on the device; resident_bytes = live HBM allocations once sandwich, matvec and transpose_matvec have all run
-        # (data + twins + index uploads; workspaces included, the allocator's cached free blocks not)
+        # the set-up timings above: synth_ms, ingest_ms, ingest_peak_bytes, data_bytes (+ ingest_rebuild_ms with --full)
         result.update(ingest)
-        result["resident_bytes"] = int(torch.cuda.memory_allocated())
-        result["ingest_note"] = ("ingest_ms: first to_device() of this process (on a fresh box it includes one-off code "
-                                 "object loads); ingest_rebuild_ms: the same twins built again on fresh wrappers of the "
-                                 "same arrays (steady state); ingest_peak_bytes: peak HBM during the first build, the "
-                                 "data included; resident_bytes: live allocations after all three products have run")
         if world > 1:
             result["ranks"] = {"backend": backend, "world_size": world,
                                "rccl_ranks": world if backend == "nccl" else 0,
                                "ms_per_step_by_rank": rank_ms, "ms_per_step_min_rank": min(rank_ms),
                                "ms_per_step_max_rank": max(rank_ms)}
-        if not args.no_cpu_baseline and world == 1:   # the CPU leg runs on rank 0 at N = 1 only
-            cpu_rows = args.cpu_rows or {"cfg4": 1_000_000, "cfg2": 2_000_000,
-                                         "cfg3": 50_000_000}.get(args.workload, 1_000_000)
-            result["cpu_baseline"] = cpu_baseline(args.workload, min(cpu_rows, n_local), mat, d)
-        if args.breakdown:
-            for k, v in sorted(bd.items(), key=lambda kv: -kv[1]):
-                print(f"  {k:24s} {v:9.4f} ms", file=sys.stderr)
-        result_full = dict(result, breakdown_ms={k: round(v, 4) for k, v in bd.items()})
+        bd = None
+        if args.full:
+            bd = kernel_breakdown(mat, d)
+            dom = max(bd, key=bd.get)
+            dom_ms = bd[dom]
+            dom_bytes = op_algorithmic_bytes(mat, dom)
+            dom_flops = op_flops(mat, dom)
+            hbm_time = dom_bytes / (HBM_PEAK_GBS * 1e9)
+            peak_tf = MFMA_F64_PEAK_TFLOPS if tdt == torch.float64 else MFMA_F32_PEAK_TFLOPS
+            mfma_note = None
+            if (dom_flops and tdt == torch.float32 and isinstance(mat, tm.DenseMatrix) and 128 < p <= 256
+                    and p % 4 == 0):
+                # the f32 syrk of 129..256 columns runs as SIX bf16 piece products on the bf16 matrix cores
+                # (csrc/syrk_bf16.hip): priced against the dense bf16 peak with the flops it really issues
+                dom_flops *= 6.0
+                peak_tf = MFMA_BF16_PEAK_TFLOPS
+                mfma_note = ("f32 syrk as 6 bf16 piece products (3-piece split, f32 accumulation): achieved = "
+                             "6 x n k (k + 1) bf16 flop / kernel time, peak = dense bf16 MFMA")
+            mfma_time = (dom_flops / (peak_tf * 1e12)) if dom_flops else 0.0
+            dom_lds = op_lds_bytes(mat, dom)
+            lds_time = (dom_lds / (LDS_PEAK_GBS * 1e9)) if dom_lds else 0.0
+            # the bounding roofline of the dominant kernel ("hbm" | "mfma"): MFMA when its matrix time
+            # exceeds its HBM time, else HBM -- `frac` is against THAT bound.  A kernel whose inner loop is an LDS
+            # gather additionally carries `frac_lds` (its algorithmic LDS bytes against the guide's aggregate LDS
+            # rate): a second opinion on what limits it, never `frac`.
+            if mfma_time > hbm_time:
+                roof = {"bound": "mfma", "achieved": round(dom_flops / (dom_ms * 1e-3) / 1e12, 3),
+                        "peak": peak_tf, "unit": "TFLOP/s"}
+            else:
+                roof = {"bound": "hbm", "achieved": round(dom_bytes / (dom_ms * 1e-3) / 1e9, 1),
+                        "peak": HBM_PEAK_GBS, "unit": "GB/s"}
+            roof["frac"] = round(roof["achieved"] / roof["peak"], 4)
+            # (the same kernel against the HBM roofline, whatever binds it)
+            roof["frac_hbm"] = round(dom_bytes / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+            if dom_lds:
+                roof["frac_lds"] = round(dom_lds / (dom_ms * 1e-3) / 1e9 / LDS_PEAK_GBS, 4)
+                roof["algorithmic_lds_bytes_per_launch"] = int(dom_lds)
+                roof["lds_peak_gbs"] = LDS_PEAK_GBS
+            # HBM bytes per launch of that kernel, measured NOW: rocprofv3 --pmc passes over a child
+            # run that launches the same op (null when rocprofv3 is unavailable or N > 1)
+            roof["traffic"] = None
+            if world == 1 and not args.no_traffic:
+                roof["traffic"] = measure_traffic(args, dom)
+            # the dense self-sandwich: against the matrix spec of its dtype when it ran on that dtype's MFMA; when it
+            # ran in 40-bit fixed point on the INT8 matrix cores (K1e) an f64-equivalent flop rate against the f64
+            # spec would not be a utilisation: it is priced against HBM (it streams the block once) and by the int8
+            # operations it issues (22 digit-pair products of n k (k + 1) / 2 MACs each, padded to 128 columns)
+            mfma_frac, dense_self = None, None
+            i8_ran = bool(dense_term and dense_term.startswith("int8"))
+            for name, ms in bd.items():
+                fl = op_flops(mat, name)
+                if not fl:
+                    continue
+                if i8_ran:
+                    by = op_algorithmic_bytes(mat, name)
+                    kk = [m for m in (mat.matrices if isinstance(mat, tm.SplitMatrix) else [mat])
+                          if isinstance(m, tm.DenseMatrix)][0].shape[1]
+                    kp = -(-kk // 128) * 128 if kk <= 128 else kk
+                    dense_self = {"kernel": name, "ms": round(ms, 4), "arithmetic": "int8x5 digits, 22 digit pairs, int32 acc",
+                                  "frac_hbm": round(by / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                  "int8_tops": round(22.0 * n_local * kp * (kp + 16) / (ms * 1e-3) / 1e12, 1),
+                                  "int8_peak_tops_dense": INT8_PEAK_TOPS}
+                else:
+                    mfma_frac = round(fl * (6.0 if mfma_note else 1.0) / (ms * 1e-3) / (peak_tf * 1e12), 4)
+            if mfma_note:
+                roof["note"] = mfma_note
+            roof["kernel"] = dom
+            roof["kernel_ms"] = round(dom_ms, 4)
+            roof["algorithmic_bytes_per_launch"] = int(dom_bytes)
+            result.update({
+                "roofline": roof,
+                "ms_per_step_min": round(ms_min, 4),
+                "hbm_frac_whole_job": round(alg_bytes / world / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                # whole step against max(HBM, MFMA): bytes / 8 TB/s vs flops / dense matrix peak of the dtype
+                "mixed_roofline_ms": round(max(alg_bytes / world / (HBM_PEAK_GBS * 1e9),
+                                               flops * (6.0 if mfma_note else 1.0) / world / (peak_tf * 1e12)) * 1e3, 4),
+                "mfma_frac_of_spec": mfma_frac,
+                "dense_self": dense_self,
+                "sum_kernel_ms": round(sum(bd.values()), 4),
+                "matvec": mv.get("matvec"),
+                "transpose_matvec": mv.get("transpose_matvec"),
+                "dense_term": dense_term,
+                "dense_term_handover": handovers,
+                "ms_per_step_f64_only": None if ms_f64_only is None else round(ms_f64_only, 4),
+                "ms_per_step_hipgraph": None if ms_graph is None else round(ms_graph, 4),
+            })
+            if args.workload == "cfg4":
+                scale = n_local / 10_000_000
+                floor = sum(v[0] for v in DESIGN_FLOOR_CFG4_MS.values()) * scale
+                result["design_floor_ms"] = round(floor, 2)
+                result["design_floor"] = {
+                    "what": ("per-GPU step time of the CURRENT formulation (one kernel per block product) with every "
+                             "kernel at the floor its own ablation shows; the north star's 0.60 of HBM peak would be "
+                             f"{alg_bytes / world / (0.6 * HBM_PEAK_GBS * 1e9) * 1e3:.2f} ms, below the f64 arithmetic of the "
+                             "dense term at any rate this chip has (SURVEY.md 8d)"),
+                    "terms_ms_at_10M_rows": {k: {"ms": v[0], "from": v[1]} for k, v in DESIGN_FLOOR_CFG4_MS.items()},
+                    "step_over_floor": round(ms_per_step / floor, 3),
+                }
+            # ingest as a measured quantity: to_device() = every twin the three products stream, built
+            # on the device; resident_bytes = live HBM allocations once sandwich, matvec and transpose_matvec have all run
+            # (data + twins + index uploads; workspaces included, the allocator's cached free blocks not)
+            result["resident_bytes"] = int(torch.cuda.memory_allocated())
+            result["ingest_note"] = ("ingest_ms: first to_device() of this process (on a fresh box it includes one-off code "
+                                     "object loads); ingest_rebuild_ms: the same twins built again on fresh wrappers of the "
+                                     "same arrays (steady state); ingest_peak_bytes: peak HBM during the first build, the "
+                                     "data included; resident_bytes: live allocations after all three products have run")
+            if not args.no_cpu_baseline and world == 1:   # the CPU leg runs on rank 0 at N = 1 only
+                cpu_rows = args.cpu_rows or {"cfg4": 1_000_000, "cfg2": 2_000_000,
+                                             "cfg3": 50_000_000}.get(args.workload, 1_000_000)
+                result["cpu_baseline"] = cpu_baseline(args.workload, min(cpu_rows, n_local), mat, d)
+            if args.breakdown:
+                for k, v in sorted(bd.items(), key=lambda kv: -kv[1]):
+                    print(f"  {k:24s} {v:9.4f} ms", file=sys.stderr)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as f:
-                json.dump(result_full, f, indent=1)
+                json.dump(result if bd is None else dict(result, breakdown_ms={k: round(v, 4) for k, v in bd.items()}),
+                          f, indent=1)
         print(json.dumps(result))
     if world > 1:
         dist.barrier()

@@ -54,6 +54,7 @@ def _abi_call_spy():
             ABI_CALLS[_name] = ABI_CALLS.get(_name, 0) + 1
             return _fn(*args)
 
+        spy.__wrapped__ = fn            # the ctypes function (argtypes), for inspect.unwrap
         setattr(handle, name, spy)
     yield
 

@@ -142,7 +142,7 @@ def test_bench_two_ranks_gloo():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "200000",
-                          "--steps", "3", "--warmup", "1", "--no-traffic", "--no-cpu-baseline"],
+                          "--steps", "3", "--warmup", "1", "--full", "--no-traffic", "--no-cpu-baseline"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -202,7 +202,7 @@ def test_bench_eight_ranks_gloo():
         env.pop(k, None)
     t0 = time.time()
     r = _bench_json([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--rows", "100000",
-                     "--steps", "3", "--warmup", "1", "--no-traffic", "--no-cpu-baseline"], env)
+                     "--steps", "3", "--warmup", "1", "--full", "--no-traffic", "--no-cpu-baseline"], env)
     wall = time.time() - t0
     assert r["n_gpus"] == 8 and r["steps"] == 3 and r["scaling"] == "weak" and r["higher_is_better"] is True
     assert r["config"]["sharding"] == "rows" and r["config"]["collective"].startswith("all_reduce")
