@@ -173,6 +173,27 @@ int tm_dense_sandwich_i8_wide_centered_f64(const double *X, int64_t n, int64_t m
 int tm_dense_sandwich_i8_history_words(void);
 int tm_dense_sandwich_i8_hist_f64(const double *X, int64_t n, int64_t m, const double *d, const double *colmax,
                                   double *out, double *colsum, int32_t *history, void *stream);
+/* SANDWICH + TRANSPOSE_MATVEC in one pass (round 7): the forms above with a second vector v (length n, f64) whose
+ * xtv = X' v (length m, overwritten) accumulates in f64 from the same pass over the block -- K1e on the raw value in
+ * its conversion step (v staged per half chunk next to sqrt(d)), K1c from its B-side fragments.  What
+ * SplitMatrix.sandwich_and_transpose_matvec needs for the IRLS step H = X' D X, g = X' (w z) without re-reading
+ * the block in a separate transpose_matvec (reference: dense_matrix.py sandwich + transpose_matvec).  colsum
+ * (X' d, K1c only: K1e with both sums spills ~240 registers) and history may be NULL.  K1e hands calls outside its
+ * envelope to K1c on the device, which then writes xtv as well.  Under a CENTRE both sums are those of X - 1 c': the caller adds c * sum(v) back for X' v.
+ * The wide form (130 .. 512 even columns) takes xtv from its diagonal 128-column panels; center may be NULL. */
+int tm_dense_sandwich_co_xtv_f64(const double *X, int64_t n, int64_t m, const double *d, const double *v,
+                                 double *out, double *colsum, double *xtv, void *stream);
+int tm_dense_sandwich_co_centered_xtv_f64(const double *X, int64_t n, int64_t m, const double *d, const double *v,
+                                          const double *center, double *out, double *colsum, double *xtv,
+                                          void *stream);
+int tm_dense_sandwich_i8_xtv_f64(const double *X, int64_t n, int64_t m, const double *d, const double *v,
+                                 const double *colmax, double *out, double *xtv, int32_t *history, void *stream);
+int tm_dense_sandwich_i8_centered_xtv_f64(const double *X, int64_t n, int64_t m, const double *d, const double *v,
+                                          const double *colmax, const double *center, double *out, double *xtv,
+                                          int32_t *history, void *stream);
+int tm_dense_sandwich_i8_wide_xtv_f64(const double *X, int64_t n, int64_t m, const double *d, const double *v,
+                                      const double *colmax, const double *center, double *out, double *xtv,
+                                      void *stream);
 
 /* X' diag(d) X of an unrestricted, 16-byte aligned, C-ordered FLOAT32 block of m = 4 k <= 256 columns
  * on the bf16 matrix cores: every element of diag(sqrt|d|) X is split into three bf16 pieces (24

@@ -57,8 +57,10 @@ int64_t tune(const char *key, int64_t dflt);
 // round 5: the 16-byte loads of an odd-width block start at 8-byte aligned addresses, which the hardware takes);
 // colsum (may be NULL) receives X' d.  syrk_co_ok() says whether a block qualifies.
 // center (may be NULL): per-column centres c -- the product (and column sums) of X - 1 c'.
+// v / xtv (may be NULL, together): xtv = X' v (of X - 1 c' with center) from the same pass.
 int run_syrk_co(const double *X, int64_t n, int64_t m, const double *d, double *out,
-                double *colsum, hipStream_t st, const double *center = nullptr);
+                double *colsum, hipStream_t st, const double *center = nullptr, const double *v = nullptr,
+                double *xtv = nullptr);
 inline bool syrk_co_ok(const void *X, int64_t m) {
     return m > 0 && m <= 128 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
 }
@@ -70,7 +72,7 @@ inline bool syrk_co_pays(int64_t m) { return m > 64; }
 // the row strides ldx / ldo of X / out -- for a 128-column panel of a wider block in place.
 int run_syrk_i8_panel(const double *X, int64_t ldx, int64_t n, int64_t m, const double *d, const double *colmax,
                       double *out, int64_t ldo, double *colsum, int *history, hipStream_t st,
-                      const double *center = nullptr);
+                      const double *center = nullptr, const double *v = nullptr, double *xtv = nullptr);
 
 // K1d (syrk_bf16.hip): X' diag(d) X of an unrestricted C-ordered f32 block of 4 k <= 256 columns on the
 // bf16 matrix cores (three-piece split, f32 accumulation); it pays above 128 columns.

@@ -612,13 +612,18 @@ static int run_dense_sandwich(const F *X, int64_t n, int64_t m, int order_f, con
 // panels run on the int8 matrix cores in place (K1e through its row strides; every panel has its own
 // envelope check and f64 hand-over), the off-diagonal panel pairs on the rectangular f64 MFMA tile set.
 // 2M x 256: two int8 panels + one rectangle instead of three f64 passes (profiles/r4_regimes.txt).
+// v / xtv (may be NULL, together): xtv = X' v, each 128-column slice from its diagonal panel's pass (K1e / K1c TV
+// form), so the whole vector falls out of the panels that stream every column once anyway.
 static int run_dense_sandwich_i8_wide(const double *X, int64_t n, int64_t m, const double *d,
                                       const double *colmax, double *out, hipStream_t st,
-                                      const double *center = nullptr) {
+                                      const double *center = nullptr, const double *v = nullptr,
+                                      double *xtv = nullptr) {
+    TM_REQUIRE((v == nullptr) == (xtv == nullptr), "v and xtv go together");
     TM_REQUIRE(m > 128 && m <= 512 && m % 2 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0,
                "a 16-byte aligned C-ordered float64 block of 130 .. 512 (even) columns");
     if (n == 0) {
         TM_HIP(hipMemsetAsync(out, 0, sizeof(double) * (size_t)(m * m), st));
+        if (xtv) TM_HIP(hipMemsetAsync(xtv, 0, sizeof(double) * (size_t)m, st));
         return TM_OK;
     }
     const int PW = 128;
@@ -627,7 +632,8 @@ static int run_dense_sandwich_i8_wide(const double *X, int64_t n, int64_t m, con
         const int wa = (int)std::min<int64_t>(PW, m - (int64_t)a * PW);
         int rc = run_syrk_i8_panel(X + (int64_t)a * PW, m, n, wa, d, colmax + (int64_t)a * PW,
                                    out + ((int64_t)a * PW) * m + (int64_t)a * PW, m, nullptr, nullptr, st,
-                                   center ? center + (int64_t)a * PW : nullptr);
+                                   center ? center + (int64_t)a * PW : nullptr, v,
+                                   xtv ? xtv + (int64_t)a * PW : nullptr);
         if (rc) return rc;
     }
     void *wsv = nullptr;
@@ -1381,6 +1387,13 @@ int tm_dense_sandwich_i8_wide_f64(const double *X, int64_t n, int64_t m, const d
 int tm_dense_sandwich_i8_wide_centered_f64(const double *X, int64_t n, int64_t m, const double *d,
                                            const double *colmax, const double *center, double *out, void *stream) {
     return tmh::run_dense_sandwich_i8_wide(X, n, m, d, colmax, out, tmh::as_stream(stream), center);
+}
+
+int tm_dense_sandwich_i8_wide_xtv_f64(const double *X, int64_t n, int64_t m, const double *d, const double *v,
+                                      const double *colmax, const double *center, double *out, double *xtv,
+                                      void *stream) {
+    TM_REQUIRE(v != nullptr && xtv != nullptr, "v and xtv are required");
+    return tmh::run_dense_sandwich_i8_wide(X, n, m, d, colmax, out, tmh::as_stream(stream), center, v, xtv);
 }
 
 // (X - 1 center')[rows, cols]' diag(d[rows]) (X - 1 center')[rows, cols]; center: length m, indexed by the column of X

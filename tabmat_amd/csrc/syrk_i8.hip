@@ -260,12 +260,18 @@ __global__ void i8_scale_kernel(const double *__restrict__ colmax, int m, int64_
 // mean-sized rank-one terms from the raw product; slicing the centred columns instead keeps the fixed point
 // (and the f64 sums) at the scale of the RESULT -- an uncentred "year" column (2000 +- 5) would otherwise lose
 // (mean / std)^2 = 1.6e5 of the 2e-14.  One more v_add_f64 per entry in the conversion's shadow.
-template <bool CSUM, bool CEN>
+// TV: X' v for a second vector v (length n) from the same pass -- v is staged per half chunk next to sqrt(d) and
+// one more v_fma_f64 per entry accumulates x v per lane in f64 on the raw (under CEN: centred) value, as CSUM does
+// for d; the IRLS gradient of SplitMatrix.sandwich_and_transpose_matvec without a second pass over the block.
+// (TV and CSUM together are not built: the four more live doubles spill ~240 registers -- scripts/regcheck.sh; TV
+// alone spills as much as the plain kernel.)
+template <bool CSUM, bool CEN, bool TV = false>
 __global__ __launch_bounds__(I8_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void syrk_i8_kernel(const double *__restrict__ X, int64_t ldx, int64_t n, int64_t m, const double *__restrict__ d,
                     const double *__restrict__ sigma, const I8Info *__restrict__ info, int n_items,
                     unsigned *__restrict__ counter, double *__restrict__ part, double *__restrict__ colsum,
-                    const double *__restrict__ center) {
+                    const double *__restrict__ center, const double *__restrict__ v = nullptr,
+                    double *__restrict__ xtv = nullptr) {
     if (info->flag != 0) return;                                          // the f64 kernel takes this call
     // SEPARATE static LDS objects: the compiler tracks LDS-DMA copies per LDS variable (alias scopes of
     // the module-LDS lowering) and makes every LDS access that may alias a copy in flight wait for it
@@ -276,6 +282,7 @@ void syrk_i8_kernel(const double *__restrict__ X, int64_t ldx, int64_t n, int64_
     __shared__ __attribute__((aligned(16))) unsigned char planes[I8_PLANES];      // [6][128][I8_PSTR]: ONE chunk
     __shared__ __attribute__((aligned(16))) unsigned char raw[3 * I8_RAWBUF];     // ring of 3 half chunks: [32 rows][I8_RAWSTR] f64
     __shared__ double dl[3 * I8_HS];                                              // sqrt(d) of the ring slots
+    __shared__ double vl[TV ? 3 * I8_HS : 1];                                     // TV: v of the ring slots
     __shared__ unsigned slot_mem[4];
     unsigned *slot = slot_mem;
 #if defined(I8_TRACE)
@@ -300,7 +307,7 @@ void syrk_i8_kernel(const double *__restrict__ X, int64_t ldx, int64_t n, int64_
 
     using C0 = std::integral_constant<int, 0>;
     using C1 = std::integral_constant<int, 1>;
-    double dreg = 0.0;
+    double dreg = 0.0, vreg = 0.0;
     const int dma_voff = lane * 2 < m ? lane * 16 : 0x7ffffff0;           // column pairs beyond the block read as 0
     // request the next half chunk into ring slot rb: wave w copies rows 8 w .. 8 w + 7
     auto issue_half = [&](int rb) -> unsigned {
@@ -318,6 +325,9 @@ void syrk_i8_kernel(const double *__restrict__ X, int64_t ldx, int64_t n, int64_
         const i8_rsrc_t rs = i8_rsrc(reinterpret_cast<const void *>((uintptr_t)(((uint64_t)xhi << 32) | xlo)), nbytes);
         // (d first: the wave that loads it waits for it with the younger copies still in flight)
         if (wave == 0 && lane < I8_HS) dreg = tb + lane < n ? d[tb + lane] : 0.0;
+        if constexpr (TV) {
+            if (wave == 0 && lane < I8_HS) vreg = tb + lane < n ? v[tb + lane] : 0.0;
+        }
 #if !defined(I8_ABLATE_NO_DMA)
 #pragma unroll
         for (int j = 0; j < 8; ++j)
@@ -333,6 +343,9 @@ void syrk_i8_kernel(const double *__restrict__ X, int64_t ldx, int64_t n, int64_
     };
     auto publish_d = [&](int rb) {          // sqrt(d) of the half just requested (wave 0, after its load landed)
         if (wave == 0 && lane < I8_HS) dl[rb * I8_HS + lane] = sqrt(dreg);
+        if constexpr (TV) {
+            if (wave == 0 && lane < I8_HS) vl[rb * I8_HS + lane] = vreg;
+        }
     };
 
     // this lane's two columns and their scales
@@ -343,6 +356,7 @@ void syrk_i8_kernel(const double *__restrict__ X, int64_t ldx, int64_t n, int64_
         cen1 = 32 * wave + 16 + cl < m ? center[32 * wave + 16 + cl] : 0.0;
     }
     double cs0 = 0.0, cs1 = 0.0;                                           // CSUM: this lane's share of X' d, columns cb = 0 / 1
+    double cv0 = 0.0, cv1 = 0.0;                                           // TV: the same of X' v
     const double MAGIC = 6755399441055744.0 + 551911719040.0;             // 1.5 * 2^52 + 0x8080808080
     // one half chunk (ring slot rb) -> rows 32 hh .. 32 hh + 31 of the digit planes.  Per call: the
     // lane's 4 rows (quad qq of 8) of column block cb (0 / 1) -- 16 calls cover the half.
@@ -385,6 +399,7 @@ void syrk_i8_kernel(const double *__restrict__ X, int64_t ldx, int64_t n, int64_
     // the MFMAs, or the MFMAs of one accumulator back to back).
     struct Conv {
         double dv[4];
+        double vv[TV ? 4 : 1];
         unsigned lo[4], hi[4];
         unsigned t[4], h[2], g[5];
     };
@@ -398,6 +413,10 @@ void syrk_i8_kernel(const double *__restrict__ X, int64_t ldx, int64_t n, int64_
         if constexpr (k == 0) {                     // sqrt(d) of the 4 rows (LDS; used from step 1 + I8_CLAT on)
 #pragma unroll
             for (int j = 0; j < 4; ++j) c.dv[j] = dl[rb * I8_HS + row0 + j];
+            if constexpr (TV) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) c.vv[j] = vl[rb * I8_HS + row0 + j];
+            }
         } else if constexpr (k >= 1 && k <= 4) {
             const double sg = cb ? sg1 : sg0;
             double xv = q.x[k - 1];
@@ -407,6 +426,10 @@ void syrk_i8_kernel(const double *__restrict__ X, int64_t ldx, int64_t n, int64_
             if constexpr (CSUM) {
                 if constexpr (cb) cs1 = __builtin_fma(u, c.dv[k - 1], cs1);
                 else cs0 = __builtin_fma(u, c.dv[k - 1], cs0);
+            }
+            if constexpr (TV) {
+                if constexpr (cb) cv1 = __builtin_fma(xv, c.vv[k - 1], cv1);
+                else cv0 = __builtin_fma(xv, c.vv[k - 1], cv0);
             }
             c.lo[k - 1] = (unsigned)__double2loint(t);
             c.hi[k - 1] = (unsigned)__double2hiint(t);
@@ -702,6 +725,16 @@ void syrk_i8_kernel(const double *__restrict__ X, int64_t ldx, int64_t n, int64_
             if (32 * wave + 16 + cl < m) atomicAdd(colsum + 32 * wave + 16 + cl, cs1);
         }
     }
+    if constexpr (TV) {
+        cv0 += __shfl_xor(cv0, 16, 64);
+        cv0 += __shfl_xor(cv0, 32, 64);
+        cv1 += __shfl_xor(cv1, 16, 64);
+        cv1 += __shfl_xor(cv1, 32, 64);
+        if (lane < 16) {
+            if (32 * wave + cl < m) atomicAdd(xtv + 32 * wave + cl, cv0);
+            if (32 * wave + 16 + cl < m) atomicAdd(xtv + 32 * wave + 16 + cl, cv1);
+        }
+    }
 }
 
 // out[i][j] = 2^-(k_i + k_j) * sum over the workgroups' partials, mirrored; a quarter tile per block
@@ -778,13 +811,18 @@ __global__ void i8_record_diag_kernel(const double *__restrict__ out, int64_t ld
 // the f64 kernel's side of the hand-over: run_syrk_co_if(flag != 0)
 int run_syrk_co_flagged(const double *X, int64_t ldx, int64_t n, int64_t m, const double *d, double *out,
                         int64_t ldo, double *colsum, const unsigned *flag, void *ws, hipStream_t st,
-                        const double *center);
+                        const double *center, const double *v, double *xtv);
 size_t syrk_co_ws_bytes();
 
 // X: first element of the block (or of a 128-column panel of a wider one), ldx / ldo: row strides of X / out
 // center (may be NULL): per-column centres c -- the product of X - 1 c' (colmax is then max |x - c| per column)
+// v / xtv (may be NULL, together): xtv = X' v (of X - 1 c' under center) from the same pass, by whichever kernel the
+// envelope selects on the device
 int run_syrk_i8_panel(const double *X, int64_t ldx, int64_t n, int64_t m, const double *d, const double *colmax,
-                      double *out, int64_t ldo, double *colsum, int *history, hipStream_t st, const double *center) {
+                      double *out, int64_t ldo, double *colsum, int *history, hipStream_t st, const double *center,
+                      const double *v, double *xtv) {
+    TM_REQUIRE((v == nullptr) == (xtv == nullptr), "v and xtv go together");
+    TM_REQUIRE(v == nullptr || colsum == nullptr, "X' d and X' v are not built into one int8 kernel");
     TM_REQUIRE(n >= 0 && m >= 0, "negative shape");
     // (any row stride / width parity: with an odd stride every other row starts at an 8-byte aligned address, which
     // the 16-byte LDS-DMA copies take -- measured 10M x 127: 2.31 ms against 6.36 ms on the element-load f64 syrk.
@@ -797,9 +835,11 @@ int run_syrk_i8_panel(const double *X, int64_t ldx, int64_t n, int64_t m, const 
     if (n == 0) {
         TM_HIP(hipMemset2DAsync(out, sizeof(double) * (size_t)ldo, 0, sizeof(double) * (size_t)m, (size_t)m, st));
         if (colsum) TM_HIP(hipMemsetAsync(colsum, 0, sizeof(double) * (size_t)m, st));
+        if (xtv) TM_HIP(hipMemsetAsync(xtv, 0, sizeof(double) * (size_t)m, st));
         return TM_OK;
     }
     if (colsum) TM_HIP(hipMemsetAsync(colsum, 0, sizeof(double) * (size_t)m, st));
+    if (xtv) TM_HIP(hipMemsetAsync(xtv, 0, sizeof(double) * (size_t)m, st));
     const int64_t n_items64 = ceil_div(n, I8_ITEM_ROWS);
     TM_REQUIRE(n_items64 < (1ll << 31), "too many rows");
     const int n_items = (int)n_items64;
@@ -824,9 +864,12 @@ int run_syrk_i8_panel(const double *X, int64_t ldx, int64_t n, int64_t m, const 
     prof_begin(st);
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(I8_THREADS), 0, st, X, ldx, n, m, d, sigma, info, n_items,
-                           counter, part, colsum, center);
+                           counter, part, colsum, center, v, xtv);
     };
-    if (center) {
+    if (v) {
+        if (center) go(syrk_i8_kernel<false, true, true>);
+        else go(syrk_i8_kernel<false, false, true>);
+    } else if (center) {
         if (colsum) go(syrk_i8_kernel<true, true>);
         else go(syrk_i8_kernel<false, true>);
     } else {
@@ -841,7 +884,8 @@ int run_syrk_i8_panel(const double *X, int64_t ldx, int64_t n, int64_t m, const 
     TM_LAUNCH_CHECK();
     // weights outside the envelope: the f64 kernel (its launches return at once when the flag is clear)
     prof_hold(true);               // (the event pair stays on the int8 kernel)
-    rc = run_syrk_co_flagged(X, ldx, n, m, d, out, ldo, colsum, &info->flag, wb + own_bytes, st, center);
+    // (the xtv the int8 kernel may have begun is overwritten there: the f64 kernel's colsum kernels store, not add)
+    rc = run_syrk_co_flagged(X, ldx, n, m, d, out, ldo, colsum, &info->flag, wb + own_bytes, st, center, v, xtv);
     prof_hold(false);
     if (rc == TM_OK && history != nullptr) {
         hipLaunchKernelGGL(i8_record_diag_kernel, dim3(1), dim3(I8_W), 0, st, out, ldo, (int)m, history);
@@ -851,8 +895,9 @@ int run_syrk_i8_panel(const double *X, int64_t ldx, int64_t n, int64_t m, const 
 }
 
 int run_syrk_i8(const double *X, int64_t n, int64_t m, const double *d, const double *colmax, double *out,
-                double *colsum, int *history, hipStream_t st, const double *center = nullptr) {
-    return run_syrk_i8_panel(X, m, n, m, d, colmax, out, m, colsum, history, st, center);
+                double *colsum, int *history, hipStream_t st, const double *center = nullptr,
+                const double *v = nullptr, double *xtv = nullptr) {
+    return run_syrk_i8_panel(X, m, n, m, d, colmax, out, m, colsum, history, st, center, v, xtv);
 }
 
 }  // namespace tmh
@@ -880,6 +925,19 @@ int tm_dense_sandwich_i8_centered_f64(const double *X, int64_t n, int64_t m, con
                                       const double *center, double *out, double *colsum, int32_t *history,
                                       void *stream) {
     return tmh::run_syrk_i8(X, n, m, d, colmax, out, colsum, history, tmh::as_stream(stream), center);
+}
+
+int tm_dense_sandwich_i8_xtv_f64(const double *X, int64_t n, int64_t m, const double *d, const double *v,
+                                 const double *colmax, double *out, double *xtv, int32_t *history, void *stream) {
+    TM_REQUIRE(v != nullptr && xtv != nullptr, "v and xtv are required");
+    return tmh::run_syrk_i8(X, n, m, d, colmax, out, nullptr, history, tmh::as_stream(stream), nullptr, v, xtv);
+}
+
+int tm_dense_sandwich_i8_centered_xtv_f64(const double *X, int64_t n, int64_t m, const double *d, const double *v,
+                                          const double *colmax, const double *center, double *out, double *xtv,
+                                          int32_t *history, void *stream) {
+    TM_REQUIRE(v != nullptr && xtv != nullptr, "v and xtv are required");
+    return tmh::run_syrk_i8(X, n, m, d, colmax, out, nullptr, history, tmh::as_stream(stream), center, v, xtv);
 }
 
 }  // extern "C"

@@ -303,6 +303,75 @@ class DenseMatrix(MatrixBase):
             return xd.dense_sandwich_co(blk, d, want_colsum=True, center=center)
         return None
 
+    def _sandwich_xtv_dev(self, d, v, rows=None, center=None):
+        """(X[rows]' diag(d[rows]) X[rows], X[rows]' v[rows]) of all columns from ONE pass over the block
+        (tm_dense_sandwich_*_xtv_f64: v rides in the syrk's pass), or None when no one-pass kernel takes the call
+        -- the caller then makes the separate transpose_matvec.  d, v: float64 device tensors; rows: int32 device
+        tensor or None, taken as masked weights like the int8 path of _sandwich_dev (a repeated row id counts per
+        occurrence, as in transpose_matvec).  With `center` both products are those of X - 1 center' and the
+        second one is returned as (X - 1 c')' v + c sum(v[rows]) = X[rows]' v[rows].  Deterministic mode keeps the
+        two passes (the int8 kernel adds its column sums with atomics)."""
+        from . import categorical_matrix as _cm
+
+        if _cm.DETERMINISTIC or d.dtype != torch.float64 or v.dtype != torch.float64 or v.ndim != 1:
+            return None
+        n = self.shape[0]
+        if rows is not None and not (SYRK_I8 and D.nlen(rows) >= I8_MASKED_ROWS_SHARE * n):
+            return None
+        blk = self._dev_c()
+        res = None
+        if SYRK_I8:
+            cmax = self._i8_colmax(center)
+            if cmax is not None:
+                key = None if center is None else "centered"
+                if rows is not None:
+                    d, v = D.masked_d(d, rows), D.masked_d(v, rows)
+                    key = "masked" if center is None else "masked-centered"
+                if self.shape[1] > 128:
+                    out, _, xtv = xd.dense_sandwich_xtv(blk, d, v.contiguous(), "i8_wide", cmax, center=center)
+                else:
+                    out, _, xtv = xd.dense_sandwich_xtv(blk, d, v.contiguous(), "i8", cmax,
+                                                        history=self._i8_history(key), center=center)
+                res = (out, xtv)
+        if res is None and rows is None and xd.co_supported(blk, d):
+            out, _, xtv = xd.dense_sandwich_xtv(blk, d, v.contiguous(), "co", center=center)
+            res = (out, xtv)
+        if res is not None and center is not None:
+            res = (res[0], res[1] + center.to(torch.float64) * v.sum(dtype=torch.float64))
+        return res
+
+    def sandwich_and_transpose_matvec(self, d, v, rows=None, cols=None):
+        """(sandwich(d, rows, cols), transpose_matvec(v, rows, cols)) with the same conventions; an unrestricted
+        C-ordered float64 block of 65 .. 512 columns gets both from ONE pass over the block (the syrk carries
+        X' v, _sandwich_xtv_dev), every other call makes the two products."""
+        from .matrix_base import _check_1d
+
+        _check_1d(v)
+        d_dev_side, v_dev_side = D.is_dev(d), D.is_dev(v)
+        if not d_dev_side:
+            d = np.asarray(d)
+        if not v_dev_side:
+            v = np.asarray(v)
+        check_sandwich_compatible(self, d)
+        check_matvec_dimensions(self, v, transpose=True)
+        n, m = self.shape
+        rows_n = normalize_index(rows, n)
+        cols_n = normalize_index(cols, m)
+        both = None
+        if (cols_n is None or (len(cols_n) == m and np.array_equal(cols_n, np.arange(m)))) \
+                and (rows_n is None or len(rows_n) < n) and self.dtype == np.float64:
+            d_dev = D.to_dev(d)
+            if d_dev.dtype == torch.float64:
+                both = self._sandwich_xtv_dev(d_dev, D.to_dev(v, torch.float64), D.idx_dev(rows_n))
+        if both is None:
+            return self.sandwich(d, rows, cols), self.transpose_matvec(v, rows, cols)
+        H, g = both
+        if not v_dev_side:
+            g = D.to_host(g)
+            if np.issubdtype(v.dtype, np.floating) and v.dtype != self.dtype:
+                g = g.astype(np.result_type(v.dtype, self.dtype))
+        return (H if d_dev_side else D.to_host(H)), g
+
     def sandwich(self, d, rows=None, cols=None):
         """X[rows, cols].T @ diag(d[rows]) @ X[rows, cols] (dense_matrix.py:153-163)."""
         on_dev = D.is_dev(d)

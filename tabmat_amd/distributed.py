@@ -5,7 +5,7 @@ row-partitioned and needs no exchange.  One process per GPU (torch.distributed, 
 = RCCL over xGMI); each rank owns a contiguous row range of EVERY block and computes a full
 p x p partial with the single-GPU kernels; the only collective on the data path is one
 all-reduce of the small result (8 MB at p = 1024) per sandwich, or of a length-p vector per
-transpose_matvec.  No NCCL pattern of the reference is translated: the reference has none.
+transpose_matvec, or of both packed into one buffer per sandwich_and_transpose_matvec.  No NCCL pattern of the reference is translated: the reference has none.
 """
 from __future__ import annotations
 
@@ -70,6 +70,7 @@ class RowShardedMatrix:
     def __init__(self, local, group=None,
                  local_sandwich: Optional[Callable] = None,
                  local_transpose_matvec: Optional[Callable] = None,
+                 local_sandwich_and_transpose_matvec: Optional[Callable] = None,
                  bounds: Optional[tuple] = None, n_global: Optional[int] = None,
                  always_reduce: bool = False):
         self.local = local
@@ -81,6 +82,12 @@ class RowShardedMatrix:
         self._sandwich = local_sandwich or (lambda d, rows, cols: local.sandwich(d, rows, cols))
         self._tmv = local_transpose_matvec or (
             lambda v, rows, cols: local.transpose_matvec(v, rows, cols))
+        if local_sandwich_and_transpose_matvec is not None:
+            self._both = local_sandwich_and_transpose_matvec
+        elif local_sandwich is None and local_transpose_matvec is None:
+            self._both = lambda d, v, rows, cols: local.sandwich_and_transpose_matvec(d, v, rows, cols)
+        else:             # (only the separate products were injected: they make the pair)
+            self._both = lambda d, v, rows, cols: (self._sandwich(d, rows, cols), self._tmv(v, rows, cols))
         self.shape = local.shape
         self.dtype = local.dtype
 
@@ -131,6 +138,36 @@ class RowShardedMatrix:
 
     def transpose_matvec(self, v, rows=None, cols=None):
         return self._all_reduce(self._tmv(v, rows, cols))
+
+    def sandwich_and_transpose_matvec(self, d, v, rows=None, cols=None):
+        """(sandwich, transpose_matvec) of one IRLS step with ONE collective: the local H (k x k) and g (length k)
+        are packed into one float64 buffer, all-reduced together and unpacked (g back in its own dtype and on
+        its own side: numpy or device, as the separate calls return it)."""
+        H, g = self._both(d, v, rows, cols)
+        if not dist.is_initialized() or (self.world_size == 1 and not self.always_reduce):
+            return H, g
+        k2 = int(np.prod(H.shape))
+        dev = next((x.device for x in (H, g) if isinstance(x, torch.Tensor)), None)
+        if dev is None:          # numpy in -> numpy out: one host buffer (_all_reduce stages it for nccl)
+            buf = self._all_reduce(np.concatenate([np.asarray(H, dtype=np.float64).ravel(),
+                                                   np.asarray(g, dtype=np.float64).ravel()]))
+            return (buf[:k2].reshape(H.shape).astype(H.dtype, copy=False),
+                    buf[k2:].reshape(g.shape).astype(g.dtype, copy=False))
+        parts = [x.reshape(-1).to(torch.float64) if isinstance(x, torch.Tensor) else
+                 torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64).ravel()).to(dev) for x in (H, g)]
+        buf = self._all_reduce(torch.cat(parts))
+
+        def back(x, y):
+            if isinstance(x, torch.Tensor):
+                return y.reshape(x.shape).to(x.dtype)
+            return y.cpu().numpy().reshape(x.shape).astype(x.dtype, copy=False)
+        return back(H, buf[:k2]), back(g, buf[k2:])
+
+    def sandwich_and_transpose_matvec_global(self, d, v, rows=None, cols=None):
+        """d, v: global length-n vectors; rows: global row ids or None."""
+        lo, hi = self.bounds
+        return self.sandwich_and_transpose_matvec(self.local_slice(d), self.local_slice(v),
+                                                  bucket_rows(rows, lo, hi), cols)
 
     def matvec(self, v, cols=None, out=None):
         """Row-partitioned output: the local rows of X v; no collective."""

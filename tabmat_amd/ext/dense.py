@@ -188,3 +188,47 @@ def dense_sandwich_i8_wide(X: DenseDev, d, colmax, center=None):
         return out
     call("tm_dense_sandwich_i8_wide_f64", D.p(X.buf), X.n, X.m, D.p(d), D.p(colmax), D.p(out), D.stream_ptr())
     return out
+
+
+def dense_sandwich_xtv(X: DenseDev, d, v, kind, colmax=None, history=None, center=None, want_colsum=False):
+    """(X' diag(d) X, X' d or None, X' v) of an unrestricted C-ordered float64 block from ONE pass over it: the
+    second vector v (length X.n, float64) rides in the syrk's own pass (tm_dense_sandwich_*_xtv_f64).
+    kind: "i8" (K1e, <= 128 columns; calls outside its envelope are handed to K1c on the device), "i8_wide" (130 ..
+    512 even columns: X' v from the diagonal 128-column panels) or "co" (K1c, <= 128 columns; want_colsum: X' d
+    as well).  center (float64, length X.m): both sums are those of X - 1 center' -- the caller adds
+    center * sum(v) back for X' v."""
+    import torch
+    from .._lib import lib
+
+    out = D.out_buf((X.m, X.m), torch.float64)
+    xtv = D.out_buf((X.m,), torch.float64)
+    cs = D.out_buf((X.m,), torch.float64) if want_colsum else None
+    D.same_float("dense_sandwich_xtv", X.buf, d, v, out)
+    assert v.numel() == X.n and v.is_contiguous() and d.numel() == X.n
+    if center is not None:
+        D.same_float("dense_sandwich_xtv", X.buf, center)
+        assert center.numel() == X.m and center.is_contiguous()
+    if kind == "co":
+        if center is not None:
+            call("tm_dense_sandwich_co_centered_xtv_f64", D.p(X.buf), X.n, X.m, D.p(d), D.p(v), D.p(center),
+                 D.p(out), D.p(cs), D.p(xtv), D.stream_ptr())
+        else:
+            call("tm_dense_sandwich_co_xtv_f64", D.p(X.buf), X.n, X.m, D.p(d), D.p(v), D.p(out), D.p(cs), D.p(xtv),
+                 D.stream_ptr())
+        return out, cs, xtv
+    assert not want_colsum, "the int8 kernels give X' d or X' v, not both"
+    D.same_float("dense_sandwich_xtv", X.buf, colmax)
+    if kind == "i8_wide":
+        call("tm_dense_sandwich_i8_wide_xtv_f64", D.p(X.buf), X.n, X.m, D.p(d), D.p(v), D.p(colmax), D.p(center),
+             D.p(out), D.p(xtv), D.stream_ptr())
+        return out, None, xtv
+    assert kind == "i8"
+    if history is not None and history.numel() < int(lib().tm_dense_sandwich_i8_history_words()):
+        raise ValueError("history needs tm_dense_sandwich_i8_history_words() int32 words")
+    if center is not None:
+        call("tm_dense_sandwich_i8_centered_xtv_f64", D.p(X.buf), X.n, X.m, D.p(d), D.p(v), D.p(colmax),
+             D.p(center), D.p(out), D.p(xtv), D.p(history), D.stream_ptr())
+    else:
+        call("tm_dense_sandwich_i8_xtv_f64", D.p(X.buf), X.n, X.m, D.p(d), D.p(v), D.p(colmax), D.p(out), D.p(xtv),
+             D.p(history), D.stream_ptr())
+    return out, None, xtv

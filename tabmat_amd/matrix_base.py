@@ -32,6 +32,13 @@ class MatrixBase(ABC):
     def sandwich(self, d, rows=None, cols=None):
         """(self[rows, cols].T * d[rows]) @ self[rows, cols] (matrix_base.py:63-76)."""
 
+    def sandwich_and_transpose_matvec(self, d, v, rows=None, cols=None):
+        """(self.sandwich(d, rows, cols), self.transpose_matvec(v, rows, cols)) -- the two products of one IRLS
+        step.  Subclasses with a one-pass kernel override it; the results follow the two calls' conventions
+        (H float64 on d's side, g on v's side).  v must be 1-D."""
+        _check_1d(v)
+        return self.sandwich(d, rows, cols), self.transpose_matvec(v, rows, cols)
+
     @abstractmethod
     def getcol(self, i: int):
         ...
@@ -129,3 +136,11 @@ def one_over_var_inf_to_val(arr: np.ndarray, val: float) -> np.ndarray:
         out = 1 / arr
     out[tiny] = val
     return out
+
+
+def _check_1d(v):
+    """sandwich_and_transpose_matvec takes one vector v (as the categorical transpose_matvec does)."""
+    if getattr(v, "ndim", None) is None:
+        v = np.asarray(v)
+    if v.ndim > 1:
+        raise NotImplementedError("sandwich_and_transpose_matvec is only implemented for 1d arrays.")

@@ -90,6 +90,18 @@ class _Centering:
         return self.vec.get(b)
 
 
+class _Xtv:
+    """The second vector of sandwich_and_transpose_matvec on its way through _sandwich_dev: v (float64 device
+    tensor over all n rows) and, per block, X_b' v[rows] over ALL of the block's columns wherever the block's
+    sandwich kernel produced it in its own pass (DenseMatrix._sandwich_xtv_dev); blocks left out get their
+    transpose_matvec launch afterwards.  Deliberately NOT the categorical shortcut of _sandwich_xtd_dev
+    (B' D 1 = (B' D C) 1 for a complete categorical C): it holds for v = d only."""
+
+    def __init__(self, v):
+        self.v = v
+        self.out = {}
+
+
 def as_tabmat(a):
     """split_matrix.py:22-37."""
     if isinstance(a, (MatrixBase, StandardizedMatrix)):
@@ -714,18 +726,20 @@ class SplitMatrix(MatrixBase):
         sel = nar["sel"]
         return full.index_select(0, sel).index_select(1, sel)
 
-    def _sandwich_dev(self, d, rows, cols_host, plan=None, colsum=None, center=None):
+    def _sandwich_dev(self, d, rows, cols_host, plan=None, colsum=None, center=None, xtv=None):
         """d: device tensor; rows: int32 device tensor or None; cols_host: host list or None.
         Returns the float64 (n_cols, n_cols) device result (split_matrix.py:324-356).
         colsum: optional list (one slot per block) that receives X_block' d[rows] (restricted to
         the block's columns) wherever it falls out of the sandwich for free.
         center (_Centering or None): dense blocks whose SELF term is computed centred (the cross terms stay
-        raw); it also records which column sums are centred."""
+        raw); it also records which column sums are centred.
+        xtv (_Xtv or None): collects X_b' v of the blocks whose self-term kernel can carry a second vector (only
+        on the unrestricted-column paths; the row-part and narrow-selection paths leave it empty)."""
         if cols_host is not None and len(cols_host) >= FULL_THEN_SELECT * self.shape[1] \
                 and len(cols_host) > 0 and self._full_product_pays_cols(cols_host):
             pos_d, sub_d, n_cols = plan if plan is not None else self._sandwich_plan(cols_host)
             cs_full = [None] * len(self.matrices) if colsum is not None else None
-            full = self._sandwich_dev(d, rows, None, None, cs_full, center=center)
+            full = self._sandwich_dev(d, rows, None, None, cs_full, center=center, xtv=xtv)
             if colsum is not None:
                 for i, c in enumerate(cs_full):
                     if c is not None:
@@ -743,7 +757,7 @@ class SplitMatrix(MatrixBase):
                 # vs 3.5 ms at 2M rows, profiles/r3_cols_rows.txt) -- the tuned unrestricted
                 # product + selection is never slower, so the cost is monotone in the selection
                 cs_full = [None] * len(self.matrices) if colsum is not None else None
-                full = self._sandwich_dev(d, rows, None, None, cs_full, center=center)
+                full = self._sandwich_dev(d, rows, None, None, cs_full, center=center, xtv=xtv)
                 if colsum is not None:
                     _, sub_sel, _ = self._sandwich_plan(cols_host)
                     for i, c in enumerate(cs_full):
@@ -758,9 +772,10 @@ class SplitMatrix(MatrixBase):
         mats = self.matrices
         empty = [sd is not None and D.nlen(sd) == 0 for sd in sub_d]
         done = set()
-        return self._sandwich_terms(d, rows, cols_host, colsum, out, pos_d, sub_d, empty, done, center)
+        return self._sandwich_terms(d, rows, cols_host, colsum, out, pos_d, sub_d, empty, done, center,
+                                    xtv if cols_host is None else None)
 
-    def _sandwich_terms(self, d, rows, cols_host, colsum, out, pos_d, sub_d, empty, done, center=None):
+    def _sandwich_terms(self, d, rows, cols_host, colsum, out, pos_d, sub_d, empty, done, center=None, xtv=None):
         """The block products of one sandwich, in line on the current stream."""
         from .ext import dense as xd
 
@@ -882,6 +897,11 @@ class SplitMatrix(MatrixBase):
                     colsum[i] = diag          # one-hot entries are 0 / 1: C' d = diag(C' D C)
                 if i not in diag_scattered:
                     xsplit.scatter_block(diag, pos_d[i], pos_d[i], out, diag=True)
+            elif (xtv is not None and colsum is None and center is None and isinstance(mi, DenseMatrix)
+                  and sub_d[i] is None and (both := mi._sandwich_xtv_dev(d, xtv.v, rows)) is not None):
+                # X_dense' v comes out of the syrk's own pass (sandwich_and_transpose_matvec)
+                res, xtv.out[i] = both
+                xsplit.scatter_block(res, pos_d[i], pos_d[i], out)
             elif (colsum is not None and colsum[i] is None and isinstance(mi, DenseMatrix)
                   and rows is None and sub_d[i] is None
                   and (both := mi._sandwich_xtd_dev(d, cen_i := (center.get(i) if center else None))) is not None):
@@ -942,6 +962,40 @@ class SplitMatrix(MatrixBase):
         cols_n = collapse_identity(normalize_index(cols, self.shape[1]), self.shape[1])
         out = self._sandwich_dev(D.to_dev(d), D.idx_dev(rows_n), cols_n)
         return out if on_dev else D.to_host(out)
+
+    def sandwich_and_transpose_matvec(self, d, v, rows=None, cols=None):
+        """(sandwich(d, rows, cols), transpose_matvec(v, rows, cols)) -- H = X' diag(d) X and g = X' v of one IRLS
+        step -- with the conventions of the two calls (H float64, numpy / device like d; g in the result dtype of
+        transpose_matvec, numpy / device like v).  The dense block's syrk carries v through its own pass (the
+        int8 / f64 syrk forms of tm_dense_sandwich_*_xtv_f64), so g costs no second read of the dense block;
+        sparse and categorical blocks, and every call the one-pass kernels do not take (row parts, narrow column
+        selections, float32, row lists below the masked-weight share, TABMAT_AMD_DETERMINISTIC=1), get the
+        transpose_matvec launches of their own afterwards: g is always complete."""
+        from .matrix_base import _check_1d
+
+        _check_1d(v)
+        d_dev_side, v_dev_side = D.is_dev(d), D.is_dev(v)
+        if not d_dev_side:
+            d = np.asarray(d)
+        if not v_dev_side:
+            v = np.asarray(v)
+        check_sandwich_compatible(self, d)
+        check_matvec_dimensions(self, v, transpose=True)
+        rows_n = normalize_index(rows, self.shape[0])
+        cols_n = collapse_identity(normalize_index(cols, self.shape[1]), self.shape[1])
+        tdt = D.torch_dtype(self.dtype)
+        v_dev = D.to_dev(v, tdt)
+        acc = None
+        if (tdt == torch.float64 and not _cm.DETERMINISTIC
+                and (rows_n is None or len(rows_n) < self.shape[0])):
+            acc = _Xtv(v_dev)
+        H = self._sandwich_dev(D.to_dev(d), D.idx_dev(rows_n), cols_n, xtv=acc)
+        g, _ = self._transpose_matvec_dev(v_dev, rows_n, cols_n, done=None if acc is None else acc.out)
+        if not v_dev_side:
+            g = D.to_host(g)
+            if np.issubdtype(v.dtype, np.floating):
+                g = g.astype(np.result_type(self.dtype, v.dtype), copy=False)
+        return (H if d_dev_side else D.to_host(H)), g
 
     def matvec(self, v, cols=None, out=None):
         """split_matrix.py:373-420."""
@@ -1017,18 +1071,11 @@ class SplitMatrix(MatrixBase):
         out += res
         return out
 
-    def transpose_matvec(self, v, rows=None, cols=None, out=None):
-        """split_matrix.py:422-460."""
-        on_dev = D.is_dev(v)
-        if not on_dev:
-            v = np.asarray(v)
-        check_matvec_dimensions(self, v, transpose=True)
-        check_transpose_matvec_out_shape(self, out)
-        if v.ndim > 1 and any(isinstance(m, CategoricalMatrix) for m in self.matrices):
-            raise NotImplementedError(
-                "CategoricalMatrix.transpose_matvec is only implemented for 1d arrays.")
-        rows_n = normalize_index(rows, self.shape[0])
-        cols_n = collapse_identity(normalize_index(cols, self.shape[1]), self.shape[1])
+    def _transpose_matvec_dev(self, v, rows_n, cols_n, done=None):
+        """The product of transpose_matvec as a device tensor of the matrix dtype, and the column selection it
+        is for.  done: {block: float64 X_b' v over all of the block's columns} from sandwich_and_transpose_matvec
+        -- those blocks are taken from there instead of launching their products (used when the product runs over
+        all columns, which is every non-empty selection: FULL_THEN_SELECT_MV)."""
         select = None
         if cols_n is not None and len(cols_n) >= FULL_THEN_SELECT_MV * self.shape[1] and len(cols_n) > 0:
             select, cols_n = cols_n, None           # all columns, the selection picked at the end
@@ -1061,7 +1108,9 @@ class SplitMatrix(MatrixBase):
             for bi, (mat, pd, scd) in enumerate(zip(self.matrices, pos_d, sub_d)):
                 if empty_rows or (scd is not None and D.nlen(scd) == 0) or bi in fused:
                     continue
-                if isinstance(mat, CategoricalMatrix):
+                if done and cols_n is None and bi in done:
+                    part = done[bi].to(tdt)
+                elif isinstance(mat, CategoricalMatrix):
                     full = D.zeros((mat.shape[1],), tdt)
                     mat._transpose_matvec_dev(v_dev, rd, scd, full)
                     part = full if scd is None else full[scd.to(torch.int64)]
@@ -1087,6 +1136,21 @@ class SplitMatrix(MatrixBase):
                     res[pd] += xs.csr_matvec_multi(mat._dev(), v_dev, rd, scd, True)
         if select is not None:
             res, cols_n = res[self._cols_dev64(select)], select
+        return res, cols_n
+
+    def transpose_matvec(self, v, rows=None, cols=None, out=None):
+        """split_matrix.py:422-460."""
+        on_dev = D.is_dev(v)
+        if not on_dev:
+            v = np.asarray(v)
+        check_matvec_dimensions(self, v, transpose=True)
+        check_transpose_matvec_out_shape(self, out)
+        if v.ndim > 1 and any(isinstance(m, CategoricalMatrix) for m in self.matrices):
+            raise NotImplementedError(
+                "CategoricalMatrix.transpose_matvec is only implemented for 1d arrays.")
+        rows_n = normalize_index(rows, self.shape[0])
+        cols_n = collapse_identity(normalize_index(cols, self.shape[1]), self.shape[1])
+        res, cols_n = self._transpose_matvec_dev(v, rows_n, cols_n)
         if not on_dev:
             res = D.to_host(res)
             if np.issubdtype(v.dtype, np.floating):

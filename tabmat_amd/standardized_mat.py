@@ -230,6 +230,16 @@ class StandardizedMatrix:
              D.p(mult_c), D.p(sum_d), k, D.stream_ptr())
         return res if on_dev else D.to_host(res)
 
+    def sandwich_and_transpose_matvec(self, d, v, rows=None, cols=None):
+        """(sandwich(d, rows, cols), transpose_matvec(v, rows, cols)): H with the centred dense terms of sandwich,
+        g = mult * (X' v) + shift * sum(v[rows]).  Two passes: the sandwich already takes X' d from the dense
+        syrk's own pass for its rank-one terms, and the int8 syrk does not carry X' d and X' v at once (the two
+        sums spill ~240 registers, csrc/syrk_i8.hip), so X' v is the transpose_matvec launch."""
+        from .matrix_base import _check_1d
+
+        _check_1d(v)
+        return self.sandwich(d, rows, cols), self.transpose_matvec(v, rows, cols)
+
     def unstandardize(self) -> MatrixBase:
         return self.mat
 
