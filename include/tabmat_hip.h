@@ -195,6 +195,22 @@ int tm_dense_sandwich_i8_wide_xtv_f64(const double *X, int64_t n, int64_t m, con
                                       const double *colmax, const double *center, double *out, double *xtv,
                                       void *stream);
 
+/* HESSIAN-VECTOR PRODUCT in one pass over a C-ordered (row-major) block, without forming X' diag(d) X:
+ *   t[i] = (X[i,:] - center) . u + shift[0] + t_add[i]      w[i] = dm[i] * t[i]      g = (X - 1 center')' w
+ * u, center, g: length m; dm, t_add, w: length n (dm holds the weights with excluded rows set to 0, so a row
+ * restriction is a masked dm).  center, shift (ONE device scalar), t_add and w may be NULL (= 0 / not
+ * written).  g is OVERWRITTEN; w, when given, is overwritten too.  Products are formed in float64 for both
+ * data types; every workgroup writes a partial g that a second launch sums in a fixed order (no atomics:
+ * bitwise reproducible).  m <= 1024 (f64) / 2048 (f32) on 16-byte aligned rows (m a multiple of 16 bytes
+ * and X 16-byte aligned), m <= 512 otherwise; TM_EINVAL beyond.  What DenseMatrix / SplitMatrix /
+ * StandardizedMatrix.sandwich_matvec run for the dense block (no counterpart in the reference). */
+int tm_dense_sandwich_matvec_f32(const float *X, int64_t n, int64_t m, const float *u, const float *dm,
+                                 const float *t_add, const float *center, const float *shift, float *g, float *w,
+                                 void *stream);
+int tm_dense_sandwich_matvec_f64(const double *X, int64_t n, int64_t m, const double *u, const double *dm,
+                                 const double *t_add, const double *center, const double *shift, double *g,
+                                 double *w, void *stream);
+
 /* X' diag(d) X of an unrestricted, 16-byte aligned, C-ordered FLOAT32 block of m = 4 k <= 256 columns
  * on the bf16 matrix cores: every element of diag(sqrt|d|) X is split into three bf16 pieces (24
  * mantissa bits) and the six leading piece products are accumulated in f32 with

@@ -408,6 +408,24 @@ class CategoricalMatrix(MatrixBase):
             full = full[D.idx_dev(cols_n, torch.int64)]
         return full if on_dev else D.to_host(full)
 
+    def sandwich_matvec(self, d, u, rows=None, cols=None):
+        """sandwich(d, rows, cols) @ u: the sandwich of a categorical block is diagonal, so this is
+        u * transpose_matvec(d, rows, cols) -- the existing histogram launch (drop_first and missing codes as in
+        sandwich), no second pass."""
+        from .matrix_base import _smv_args
+
+        a = _smv_args(self, d, u, rows, cols)
+        if a.trivial is not None:
+            return a.finish(a.trivial)
+        d_dev = D.to_dev(a.d)
+        diag = D.zeros((self.shape[1],), d_dev.dtype)
+        if self.shape[0] > 0:
+            self._transpose_matvec_dev(d_dev, D.idx_dev(a.rows), None, diag)
+        if a.cols is not None:
+            diag = diag[D.idx_dev(a.cols, torch.int64)]
+        tdt = D.torch_dtype(a.out_dtype) if a.out_dtype in (np.float32, np.float64) else torch.float64
+        return a.finish(diag.to(tdt) * D.to_dev(a.u, tdt))
+
     def _sandwich_diag_dev(self, d, rows, cols):
         """Diagonal of X' diag(d) X as a device vector (restricted to cols)."""
         if DETERMINISTIC and self.shape[0] > 0 and self.shape[1] > 0:

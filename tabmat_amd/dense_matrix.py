@@ -372,6 +372,49 @@ class DenseMatrix(MatrixBase):
                 g = g.astype(np.result_type(v.dtype, self.dtype))
         return (H if d_dev_side else D.to_host(H)), g
 
+    def _smv_block(self):
+        """The C-ordered device block when tm_dense_sandwich_matvec_* takes it (an F-ordered block through its
+        row-major twin), else None."""
+        blk = self._dev_c()
+        return blk if xd.sandwich_matvec_supported(blk) else None
+
+    def _smv_dev(self, dm, u_full, shift=None, centers=None):
+        """SplitMatrix._smv_dev for a lone dense block: (g, w, fix) from one pass, or None when the kernel does
+        not take the block.  centers: {0: column centres} or None."""
+        blk = self._smv_block()
+        if blk is None:
+            return None
+        c = None if centers is None else centers.get(0)
+        if c is not None:
+            c = c.to(u_full.dtype).contiguous()
+            cu = (c * u_full).sum().reshape(1)
+            shift = cu if shift is None else shift + cu
+        g, w = xd.dense_sandwich_matvec(blk, u_full.contiguous(), dm, center=c,
+                                        shift=None if shift is None else shift.to(u_full.dtype).contiguous(),
+                                        want_w=True)
+        return g, w, (None if c is None else (None, c))
+
+    def sandwich_matvec(self, d, u, rows=None, cols=None):
+        """sandwich(d, rows, cols) @ u without forming the sandwich (MatrixBase.sandwich_matvec).  ONE pass over
+        the block (tm_dense_sandwich_matvec_*): C-ordered blocks, and F-ordered ones through their row-major
+        twin, of at most 1024 (float64) / 2048 (float32) columns; a row restriction is a masked d, a column
+        restriction zeros in u.  The composition transpose_matvec(d * matvec(u)) runs instead for an F-ordered
+        block without a twin, wider blocks, and restricted calls on a block holding inf / nan (0 * inf of an
+        excluded row or column would leak a NaN)."""
+        from .matrix_base import _smv_args, _smv_compose
+
+        a = _smv_args(self, d, u, rows, cols)
+        if a.trivial is not None:
+            return a.finish(a.trivial)
+        blk = self._smv_block()
+        if blk is None or ((rows is not None or cols is not None) and not self._values_finite()):
+            return a.finish(_smv_compose(self, a))
+        tdt = D.torch_dtype(self.dtype)
+        g, _ = xd.dense_sandwich_matvec(blk, a.u_full(tdt).contiguous(), a.d_masked(tdt))
+        if a.cols is not None:
+            g = g[D.idx_dev(a.cols, torch.int64)]
+        return a.finish(g)
+
     def sandwich(self, d, rows=None, cols=None):
         """X[rows, cols].T @ diag(d[rows]) @ X[rows, cols] (dense_matrix.py:153-163)."""
         on_dev = D.is_dev(d)

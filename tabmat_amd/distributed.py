@@ -5,7 +5,8 @@ row-partitioned and needs no exchange.  One process per GPU (torch.distributed, 
 = RCCL over xGMI); each rank owns a contiguous row range of EVERY block and computes a full
 p x p partial with the single-GPU kernels; the only collective on the data path is one
 all-reduce of the small result (8 MB at p = 1024) per sandwich, or of a length-p vector per
-transpose_matvec, or of both packed into one buffer per sandwich_and_transpose_matvec.  No NCCL pattern of the reference is translated: the reference has none.
+transpose_matvec, or of both packed into one buffer per sandwich_and_transpose_matvec, or of the length-k result of
+sandwich_matvec.  No NCCL pattern of the reference is translated: the reference has none.
 """
 from __future__ import annotations
 
@@ -71,6 +72,7 @@ class RowShardedMatrix:
                  local_sandwich: Optional[Callable] = None,
                  local_transpose_matvec: Optional[Callable] = None,
                  local_sandwich_and_transpose_matvec: Optional[Callable] = None,
+                 local_sandwich_matvec: Optional[Callable] = None,
                  bounds: Optional[tuple] = None, n_global: Optional[int] = None,
                  always_reduce: bool = False):
         self.local = local
@@ -88,6 +90,7 @@ class RowShardedMatrix:
             self._both = lambda d, v, rows, cols: local.sandwich_and_transpose_matvec(d, v, rows, cols)
         else:             # (only the separate products were injected: they make the pair)
             self._both = lambda d, v, rows, cols: (self._sandwich(d, rows, cols), self._tmv(v, rows, cols))
+        self._smv = local_sandwich_matvec or (lambda d, u, rows, cols: local.sandwich_matvec(d, u, rows, cols))
         self.shape = local.shape
         self.dtype = local.dtype
 
@@ -168,6 +171,16 @@ class RowShardedMatrix:
         lo, hi = self.bounds
         return self.sandwich_and_transpose_matvec(self.local_slice(d), self.local_slice(v),
                                                   bucket_rows(rows, lo, hi), cols)
+
+    def sandwich_matvec(self, d, u, rows=None, cols=None):
+        """sandwich(d, rows, cols) @ u of the whole matrix: the local product (u replicated on every rank,
+        rows LOCAL ids) and ONE all-reduce of the length-k result."""
+        return self._all_reduce(self._smv(d, u, rows, cols))
+
+    def sandwich_matvec_global(self, d, u, rows=None, cols=None):
+        """d: global length-n vector; rows: global row ids or None; u: replicated."""
+        lo, hi = self.bounds
+        return self.sandwich_matvec(self.local_slice(d), u, bucket_rows(rows, lo, hi), cols)
 
     def matvec(self, v, cols=None, out=None):
         """Row-partitioned output: the local rows of X v; no collective."""

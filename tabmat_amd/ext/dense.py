@@ -232,3 +232,36 @@ def dense_sandwich_xtv(X: DenseDev, d, v, kind, colmax=None, history=None, cente
         call("tm_dense_sandwich_i8_xtv_f64", D.p(X.buf), X.n, X.m, D.p(d), D.p(v), D.p(colmax), D.p(out), D.p(xtv),
              D.p(history), D.stream_ptr())
     return out, None, xtv
+
+
+# widest block tm_dense_sandwich_matvec_* takes: 64 lanes x 8 loads of 16 bytes per row (rows 16-byte aligned),
+# of one element otherwise (csrc/sandwich_matvec.hip)
+SANDWICH_MATVEC_MAX_BYTES = 64 * 8 * 16
+SANDWICH_MATVEC_MAX_UNALIGNED = 64 * 8
+
+
+def sandwich_matvec_supported(X: DenseDev) -> bool:
+    """True when tm_dense_sandwich_matvec_* takes the block: C-ordered, at most 1024 (f64) / 2048 (f32) columns
+    on 16-byte aligned rows, at most 512 otherwise."""
+    if X.order_f or X.m == 0:
+        return False
+    es = X.buf.element_size()
+    aligned = (X.m * es) % 16 == 0 and X.buf.data_ptr() % 16 == 0
+    return X.m * es <= SANDWICH_MATVEC_MAX_BYTES if aligned else X.m <= SANDWICH_MATVEC_MAX_UNALIGNED
+
+
+def dense_sandwich_matvec(X: DenseDev, u, dm, t_add=None, center=None, shift=None, want_w=False):
+    """(g, w or None) with t = (X - 1 center') u + shift + t_add, w = dm * t, g = (X - 1 center)' w from ONE pass
+    over a C-ordered block (tm_dense_sandwich_matvec_*).  u, center: length X.m; dm, t_add: length X.n; shift: a
+    one-element device tensor; all of the block's dtype.  center / shift / t_add may be None."""
+    g = D.out_buf((X.m,), X.dtype)
+    w = D.out_buf((X.n,), X.dtype) if want_w else None
+    D.same_float("dense_sandwich_matvec", X.buf, u, dm, t_add, center, shift)
+    assert sandwich_matvec_supported(X)
+    assert u.numel() == X.m and dm.numel() == X.n and u.is_contiguous() and dm.is_contiguous()
+    assert t_add is None or (t_add.numel() == X.n and t_add.is_contiguous())
+    assert center is None or (center.numel() == X.m and center.is_contiguous())
+    assert shift is None or shift.numel() == 1
+    call(f"tm_dense_sandwich_matvec_{D.fsuf(X.buf)}", D.p(X.buf), X.n, X.m, D.p(u), D.p(dm), D.p(t_add),
+         D.p(center), D.p(shift), D.p(g), D.p(w), D.stream_ptr())
+    return g, w

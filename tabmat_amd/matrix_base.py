@@ -39,6 +39,17 @@ class MatrixBase(ABC):
         _check_1d(v)
         return self.sandwich(d, rows, cols), self.transpose_matvec(v, rows, cols)
 
+    def sandwich_matvec(self, d, u, rows=None, cols=None):
+        """self[rows, cols].T @ (d[rows] * (self[rows, cols] @ u)): sandwich(d, rows, cols) @ u without forming
+        the (k, k) sandwich (a Hessian-vector product; a repeated row id counts once per occurrence).  u has
+        length k = len(cols) (all columns when None), and so does the result: numpy for numpy u, a device
+        tensor for a device u, in numpy's dtype of sandwich(d, rows, cols) @ u.  This default composes matvec
+        and transpose_matvec; classes with a one-pass path override it."""
+        a = _smv_args(self, d, u, rows, cols)
+        if a.trivial is not None:
+            return a.finish(a.trivial)
+        return a.finish(_smv_compose(self, a))
+
     @abstractmethod
     def getcol(self, i: int):
         ...
@@ -144,3 +155,82 @@ def _check_1d(v):
         v = np.asarray(v)
     if v.ndim > 1:
         raise NotImplementedError("sandwich_and_transpose_matvec is only implemented for 1d arrays.")
+
+
+class _SmvArgs:
+    """The checked arguments of one sandwich_matvec call (_smv_args)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def finish(self, g):
+        """g (device tensor of length k) on u's side, in the result dtype."""
+        import torch
+
+        from . import _device as D
+
+        if self.on_dev:
+            return g.to(D.torch_dtype(self.out_dtype)) if self.out_dtype in (np.float32, np.float64) else g
+        return D.to_host(g).astype(self.out_dtype, copy=False)
+
+    def u_full(self, tdt):
+        """u as a device vector over ALL columns of the matrix (zeros outside `cols`; a repeated column id adds
+        up, as in self[:, cols] @ u)."""
+        import torch
+
+        from . import _device as D
+
+        u = D.to_dev(self.u, tdt)
+        if self.cols is None:
+            return u
+        full = torch.zeros((self.p,), dtype=tdt, device=u.device)
+        full.index_add_(0, D.idx_dev(self.cols, torch.int64), u)
+        return full
+
+    def d_masked(self, tdt):
+        """d as a device vector with the rows outside `rows` set to 0 (a repeated id counts per occurrence)."""
+        from . import _device as D
+
+        return D.masked_d(D.to_dev(self.d, tdt), D.idx_dev(self.rows)).contiguous()
+
+
+def _smv_args(mat, d, u, rows, cols, h_dtype=None):
+    """Host-side checks of sandwich_matvec (no device work): d as in sandwich (check_sandwich_compatible), u 1-D
+    of length len(cols) (or the number of columns).  h_dtype: the dtype sandwich() returns (default: the
+    matrix dtype).  .trivial is the result (a device tensor) when rows or cols are empty, else None."""
+    import torch
+
+    from . import _device as D
+    from .util import check_sandwich_compatible, normalize_index, np_dtype_of
+
+    if not D.is_dev(d):
+        d = np.asarray(d)
+    on_dev = D.is_dev(u)
+    if not on_dev:
+        u = np.asarray(u)
+    if u.ndim > 1:
+        raise NotImplementedError("sandwich_matvec is only implemented for 1d arrays.")
+    check_sandwich_compatible(mat, d)
+    n, p = mat.shape
+    rows_n = normalize_index(rows, n)
+    cols_n = normalize_index(cols, p)
+    k = p if cols_n is None else len(cols_n)
+    if u.ndim != 1 or u.shape[0] != k:
+        raise ValueError(f"u has shape {tuple(u.shape)}; sandwich_matvec needs length {k} (the selected columns)")
+    out_dtype = np.result_type(np.dtype(h_dtype if h_dtype is not None else mat.dtype), np_dtype_of(u))
+    trivial = None
+    if k == 0 or (rows_n is not None and len(rows_n) == 0):
+        tdt = D.torch_dtype(out_dtype) if out_dtype in (np.float32, np.float64) else torch.float64
+        trivial = D.zeros((k,), tdt)
+    return _SmvArgs(mat=mat, d=d, u=u, rows=rows_n, cols=cols_n, n=n, p=p, k=k, on_dev=on_dev,
+                    out_dtype=out_dtype, trivial=trivial)
+
+
+def _smv_compose(mat, a):
+    """transpose_matvec(d * matvec(u), rows, cols) on the device: the two-pass form of sandwich_matvec."""
+    from . import _device as D
+
+    tdt = D.torch_dtype(mat.dtype)
+    t = mat.matvec(a.u_full(tdt), cols=a.cols)
+    w = D.to_dev(a.d, tdt) * t
+    return mat.transpose_matvec(w, rows=a.rows, cols=a.cols)

@@ -18,6 +18,7 @@ from . import _device as D
 from .categorical_matrix import CategoricalMatrix
 from .dense_matrix import DenseMatrix
 from .ext import split as xsplit
+from .ext.dense import dense_sandwich_matvec as xd_smv
 from .matrix_base import MatrixBase
 from .sparse_matrix import SparseMatrix
 from .standardized_mat import StandardizedMatrix
@@ -997,6 +998,31 @@ class SplitMatrix(MatrixBase):
                 g = g.astype(np.result_type(self.dtype, v.dtype), copy=False)
         return (H if d_dev_side else D.to_host(H)), g
 
+    def sandwich_matvec(self, d, u, rows=None, cols=None):
+        """sandwich(d, rows, cols) @ u without forming the (k, k) sandwich (MatrixBase.sandwich_matvec), result
+        dtype that of the float64 sandwich @ u.  The widest dense block the one-pass kernel takes
+        (tm_dense_sandwich_matvec_*, DenseMatrix.sandwich_matvec) is read ONCE: the other blocks' matvec
+        (the fused multi-categorical and CSR kernels) runs first, the dense pass adds its own row sums, forms
+        w = d * X u and its slice of g, and the other blocks' transpose_matvec runs on w (deterministic kernels
+        under TABMAT_AMD_DETERMINISTIC=1).  Rows are a masked d, columns zeros in u -- the latter only while no
+        block holds inf / nan.  Composition of matvec and transpose_matvec otherwise: no dense block the kernel
+        takes, row parts, restricted calls on non-finite blocks."""
+        from .matrix_base import _smv_args, _smv_compose
+
+        a = _smv_args(self, d, u, rows, cols, h_dtype=np.float64)
+        if a.trivial is not None:
+            return a.finish(a.trivial)
+        tdt = D.torch_dtype(self.dtype)
+        res = None
+        if (rows is None and cols is None) or self._blocks_finite():
+            res = self._smv_dev(a.d_masked(tdt), a.u_full(tdt))
+        if res is None:
+            return a.finish(_smv_compose(self, a))
+        g = res[0]
+        if a.cols is not None:
+            g = g[self._cols_dev64(a.cols)]
+        return a.finish(g)
+
     def matvec(self, v, cols=None, out=None):
         """split_matrix.py:373-420."""
         assert not sps.issparse(v)
@@ -1017,40 +1043,15 @@ class SplitMatrix(MatrixBase):
             vm = torch.zeros_like(v_dev)
             vm[cd] = v_dev[cd]
             v_dev, cols_n = vm, None
-        _, sub_d, _ = self._sandwich_plan(cols_n)
-        idx_d = self._full_dev_indices()
         if v_dev.ndim == 1:
-            res = D.zeros((self.shape[0],), tdt)
-            fused = set()
-            plan = self._cat_hist_plan() if CAT_PAIRS_FUSED else None
-            if plan is not None:
-                # all categorical blocks in ONE pass (one gather + one launch per block before:
-                # 20 categoricals 0.33 ms for 0.18 GB); a column selection becomes zeros in the
-                # coefficient vector these blocks read
-                cl = [(self.matrices[i]._dev(), self.matrices[i].shape[1], self.matrices[i].drop_first)
-                      for i in plan.cat_ids]
-                vm = v_dev
-                if cols_n is not None:
-                    cd = self._cols_dev64(cols_n)
-                    vm = torch.zeros_like(v_dev)
-                    vm[cd] = v_dev[cd]
-                xsplit.multi_cat_matvec(plan, cl, vm, res)
-                fused = set(plan.cat_ids)
-            for bi, (mat, idx, scd) in enumerate(zip(self.matrices, idx_d, sub_d)):
-                if (scd is not None and D.nlen(scd) == 0) or bi in fused:
-                    continue
-                vb = v_dev[idx]
-                if isinstance(mat, CategoricalMatrix):
-                    mat._matvec_dev(vb, scd, res)
-                else:
-                    if scd is not None and D.nlen(scd) == mat.shape[1]:
-                        scd = None
-                    mat._matvec_dev(vb, None, scd, res, False)
+            res = self._matvec1_dev(v_dev, cols_n)
         else:
             # 2-D operand (no categorical block here): one multi-right-hand-side launch per block
             from .ext import dense as xd
             from .ext import sparse as xs
 
+            _, sub_d, _ = self._sandwich_plan(cols_n)
+            idx_d = self._full_dev_indices()
             res = D.zeros((self.shape[0], v_dev.shape[1]), tdt)
             for mat, idx, scd in zip(self.matrices, idx_d, sub_d):
                 if scd is not None and D.nlen(scd) == 0:
@@ -1070,6 +1071,74 @@ class SplitMatrix(MatrixBase):
             return res
         out += res
         return out
+
+    def _matvec1_dev(self, v_dev, cols_n, skip=()):
+        """X[:, cols] v[cols] of a 1-D device v (full length p, the matrix dtype) as a new device vector; the
+        blocks listed in `skip` are left out (sandwich_matvec adds its fused dense block itself)."""
+        _, sub_d, _ = self._sandwich_plan(cols_n)
+        idx_d = self._full_dev_indices()
+        res = D.zeros((self.shape[0],), v_dev.dtype)
+        fused = set()
+        plan = self._cat_hist_plan() if CAT_PAIRS_FUSED else None
+        if plan is not None:
+            # all categorical blocks in ONE pass (one gather + one launch per block before:
+            # 20 categoricals 0.33 ms for 0.18 GB); a column selection becomes zeros in the
+            # coefficient vector these blocks read
+            cl = [(self.matrices[i]._dev(), self.matrices[i].shape[1], self.matrices[i].drop_first)
+                  for i in plan.cat_ids]
+            vm = v_dev
+            if cols_n is not None:
+                cd = self._cols_dev64(cols_n)
+                vm = torch.zeros_like(v_dev)
+                vm[cd] = v_dev[cd]
+            xsplit.multi_cat_matvec(plan, cl, vm, res)
+            fused = set(plan.cat_ids)
+        for bi, (mat, idx, scd) in enumerate(zip(self.matrices, idx_d, sub_d)):
+            if (scd is not None and D.nlen(scd) == 0) or bi in fused or bi in skip:
+                continue
+            vb = v_dev[idx]
+            if isinstance(mat, CategoricalMatrix):
+                mat._matvec_dev(vb, scd, res)
+            else:
+                if scd is not None and D.nlen(scd) == mat.shape[1]:
+                    scd = None
+                mat._matvec_dev(vb, None, scd, res, False)
+        return res
+
+    def _smv_dense_block(self):
+        """Index of the dense block sandwich_matvec reads in its fused pass: the widest one the kernel takes
+        (tm_dense_sandwich_matvec_*), or None."""
+        best = None
+        for bi, mb in enumerate(self.matrices):
+            if isinstance(mb, DenseMatrix) and mb.shape[0] > 0 and mb._smv_block() is not None \
+                    and (best is None or mb.shape[1] > self.matrices[best].shape[1]):
+                best = bi
+        return best
+
+    def _smv_dev(self, dm, u_full, shift=None, centers=None):
+        """(g, w) with t = X u_full + shift, w = dm * t, g = X' w over ALL columns (device, the matrix dtype), or
+        None when no dense block takes the fused pass.  The other blocks' X_b u_b (t_o) comes first; one pass
+        over the fused dense block D then gives g_D and w = dm * (X_D u_D + t_o + shift); the other blocks'
+        transpose_matvec runs on w.  Returns (g, w, fix).  centers ({block: column centres} or None): D is read
+        centred -- t is the same, g_D comes back as (X_D - 1 c')' w and fix = (positions of D, c): the caller adds
+        c sum(w) there (fix is None otherwise).  shift: one-element device tensor or None."""
+        bi = self._smv_dense_block()
+        if bi is None or self._parts() is not None:
+            return None
+        mat = self.matrices[bi]
+        blk = mat._smv_block()
+        idx = self._full_dev_indices()[bi]
+        u_D = u_full[idx].contiguous()
+        t_o = self._matvec1_dev(u_full, None, skip=(bi,))
+        c = None if centers is None else centers.get(bi)
+        if c is not None:
+            c = c.to(u_full.dtype).contiguous()
+            cu = (c * u_D).sum().reshape(1)
+            shift = cu if shift is None else shift + cu
+        g_D, w = xd_smv(blk, u_D, dm, t_add=t_o, center=c,
+                        shift=None if shift is None else shift.to(u_full.dtype).contiguous(), want_w=True)
+        g, _ = self._transpose_matvec_dev(w, None, None, done={bi: g_D})
+        return g, w, (None if c is None else (idx, c))
 
     def _transpose_matvec_dev(self, v, rows_n, cols_n, done=None):
         """The product of transpose_matvec as a device tensor of the matrix dtype, and the column selection it

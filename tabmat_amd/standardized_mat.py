@@ -240,6 +240,46 @@ class StandardizedMatrix:
         _check_1d(v)
         return self.sandwich(d, rows, cols), self.transpose_matvec(v, rows, cols)
 
+    def sandwich_matvec(self, d, u, rows=None, cols=None):
+        """sandwich(d, rows, cols) @ u without forming the sandwich: with X_s = X diag(mult) + 1 shift',
+        t = X (mult u) + shift . u, w = d[rows] t, g = mult (X' w) + shift sum(w).  The inner matrix's one-pass
+        product (DenseMatrix / SplitMatrix._smv_dev) runs with the column centres of its fused dense block
+        (float64, as in sandwich): that block is read as X - 1 c', so t does not cancel mean-sized terms.
+        Composition of matvec and transpose_matvec otherwise."""
+        from .matrix_base import _smv_args, _smv_compose
+
+        a = _smv_args(self, d, u, rows, cols, h_dtype=np.float64)
+        if a.trivial is not None:
+            return a.finish(a.trivial)
+        tdt = D.torch_dtype(self.dtype)
+        mat = self.mat
+        res = None
+        finite = getattr(mat, "_blocks_finite", None) or getattr(mat, "_values_finite", None)
+        if hasattr(mat, "_smv_dev") and ((rows is None and cols is None) or finite()):
+            u_full = a.u_full(tdt)
+            au = u_full if self.mult is None else u_full * self._mult_dev(None, tdt)
+            s0 = (self._shift_dev(None, tdt) * u_full).sum().reshape(1)
+            cen = self._centering() if tdt == torch.float64 else None
+            res = mat._smv_dev(a.d_masked(tdt), au.contiguous(), shift=s0,
+                               centers=None if cen is None else cen[2])
+        if res is None:
+            return a.finish(_smv_compose(self, a))
+        g, w, fix = res
+        sw = w.sum(dtype=torch.float64).to(tdt)
+        if fix is not None:
+            pos, c = fix
+            if pos is None:
+                g = g + c * sw
+            else:
+                g = g.clone()
+                g[pos] += c * sw
+        if self.mult is not None:
+            g = g * self._mult_dev(None, tdt)
+        g = g + self._shift_dev(None, tdt) * sw
+        if a.cols is not None:
+            g = g[D.idx_dev(a.cols, torch.int64)]
+        return a.finish(g)
+
     def unstandardize(self) -> MatrixBase:
         return self.mat
 
