@@ -211,6 +211,20 @@ int tm_dense_sandwich_matvec_f64(const double *X, int64_t n, int64_t m, const do
                                  const double *t_add, const double *center, const double *shift, double *g,
                                  double *w, void *stream);
 
+/* K8d: out[j] = sum_r dm[r] (X[r][j] - center[j])^2 over a row-major (n, m) block -- the diagonal of
+ * (X - 1 center')' diag(dm) (X - 1 center') without the (m, m) product; center may be NULL, out is overwritten.
+ * dm: the weights with the excluded rows at 0.  K8's row walk without its dot product: rows through registers
+ * with 16-byte non-temporal loads, per-lane float64 column accumulators (the difference and the square are
+ * formed in float64 for both data types), per-workgroup partials summed in a fixed order by the second
+ * launch K8 uses (no atomics: bitwise reproducible).  Width limits as tm_dense_sandwich_matvec_*: m <= 1024
+ * (f64) / 2048 (f32) on 16-byte aligned rows, m <= 512 otherwise; TM_EINVAL beyond.  What
+ * DenseMatrix / SplitMatrix / StandardizedMatrix.sandwich_diag run for a dense block (no counterpart in the
+ * reference). */
+int tm_dense_sandwich_diag_f32(const float *X, int64_t n, int64_t m, const float *dm, const float *center,
+                               float *out, void *stream);
+int tm_dense_sandwich_diag_f64(const double *X, int64_t n, int64_t m, const double *dm, const double *center,
+                               double *out, void *stream);
+
 /* X' diag(d) X of an unrestricted, 16-byte aligned, C-ordered FLOAT32 block of m = 4 k <= 256 columns
  * on the bf16 matrix cores: every element of diag(sqrt|d|) X is split into three bf16 pieces (24
  * mantissa bits) and the six leading piece products are accumulated in f32 with
@@ -530,6 +544,23 @@ int tm_csr_rmatvec_u16_f32(const float *csr_data, const uint16_t *csr_indices16,
                            int64_t n, int64_t m, const float *v, float *out, void *stream);
 int tm_csr_rmatvec_u16_f64(const double *csr_data, const uint16_t *csr_indices16, const int64_t *csr_indptr,
                            int64_t n, int64_t m, const double *v, double *out, void *stream);
+
+/* K7b: s2[j] += sum_i dm[i] X[i, j]^2 and, when s1 is not NULL, s1[j] += sum_i dm[i] X[i, j], both from ONE read
+ * of every entry of the CSR twin (all rows, all columns; dm: the weights with the excluded rows at 0) -- the
+ * diagonal of X' diag(dm) X and the first moment StandardizedMatrix.sandwich_diag centres it with.  The
+ * transpose_matvec stream kernel with two LDS bin arrays; _u16: on the 16-bit column twin (m <= 65536).  Values
+ * and columns must start at entries of the same parity.  The bins must fit the LDS:
+ * 8 * k * ((m + 1) & ~1) + sizeof(F) * 4096 <= 128 KB with k = 2 (s1 given: m <= 6144 f64 / 7168 f32) or k = 1
+ * (s1 NULL: m <= 12288 f64 / 14336 f32); TM_EINVAL beyond -- the caller then runs tm_csr_rmatvec_* and
+ * tm_csr_col_sq_*.  Sums as in tm_csr_rmatvec_* (LDS atomics: not bitwise reproducible). */
+int tm_csr_sandwich_diag_u16_f32(const float *csr_data, const uint16_t *csr_indices16, const int64_t *csr_indptr,
+                                 int64_t n, int64_t m, const float *dm, float *s1, float *s2, void *stream);
+int tm_csr_sandwich_diag_u16_f64(const double *csr_data, const uint16_t *csr_indices16, const int64_t *csr_indptr,
+                                 int64_t n, int64_t m, const double *dm, double *s1, double *s2, void *stream);
+int tm_csr_sandwich_diag_f32(const float *csr_data, const int32_t *csr_indices, const int64_t *csr_indptr,
+                             int64_t n, int64_t m, const float *dm, float *s1, float *s2, void *stream);
+int tm_csr_sandwich_diag_f64(const double *csr_data, const int32_t *csr_indices, const int64_t *csr_indptr,
+                             int64_t n, int64_t m, const double *dm, double *s1, double *s2, void *stream);
 
 /* out[Cj] += sum_{i in rows} X[i, cols[Cj]] * v[i]      (v length n; out length n_cols).
  * Replaces csc_rmatvec_unrestricted / csc_rmatvec (ext/sparse.pyx:142-199).  The reference

@@ -426,6 +426,19 @@ class CategoricalMatrix(MatrixBase):
         tdt = D.torch_dtype(a.out_dtype) if a.out_dtype in (np.float32, np.float64) else torch.float64
         return a.finish(diag.to(tdt) * D.to_dev(a.u, tdt))
 
+    def sandwich_diag(self, d, rows=None, cols=None):
+        """diag(sandwich(d, rows, cols)): the weighted level counts the sandwich itself is made of
+        (_sandwich_diag_dev; drop_first and missing codes as in sandwich), as a vector."""
+        from .matrix_base import _sd_args
+
+        a = _sd_args(self, d, rows, cols)
+        if a.trivial is not None:
+            return a.finish(a.trivial)
+        diag = self._sandwich_diag_dev(D.to_dev(a.d), D.idx_dev(a.rows), None)
+        if a.cols is not None:
+            diag = diag[D.idx_dev(a.cols, torch.int64)]
+        return a.finish(diag)
+
     def _sandwich_diag_dev(self, d, rows, cols):
         """Diagonal of X' diag(d) X as a device vector (restricted to cols)."""
         if DETERMINISTIC and self.shape[0] > 0 and self.shape[1] > 0:

@@ -304,17 +304,22 @@ __global__ __launch_bounds__(CSR_WAVES * 64) void csr_matvec_stream_kernel(
     }
 }
 
-template <typename F, typename IDX = int32_t>
+// MOM = 2: both moments, sum v x and sum v x^2, from one read of the entry (two bin arrays; the partials of the second
+// one follow those of all workgroups' first: ws[gridDim.x][m] twice; `square` is not read)
+template <typename F, typename IDX = int32_t, int MOM = 1>
 __global__ __launch_bounds__(CSR_WAVES * 64) void csr_rmatvec_stream_kernel(
     const F *__restrict__ data, const IDX *__restrict__ ind, const int64_t *__restrict__ ptr,
     const F *__restrict__ v, int64_t n, int m, int64_t chunks_per_wave, F *__restrict__ ws,
     int square) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    lds_acc_t *bins = reinterpret_cast<lds_acc_t *>(smem_raw);     // [m] doubles
+    lds_acc_t *bins = reinterpret_cast<lds_acc_t *>(smem_raw);     // [m] doubles (x 2 with both moments)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    F *vrow = reinterpret_cast<F *>(bins + ((m + 1) & ~1)) + wave * CSR_CAP;    // [CSR_CAP] per wave, 16-byte aligned
-    for (int j = threadIdx.x; j < m; j += blockDim.x) bins[j] = 0.0;
+    const int mp = (m + 1) & ~1;
+    const int nbin = MOM * mp;
+    lds_acc_t *bins2 = bins + mp;                                  // (MOM == 2)
+    F *vrow = reinterpret_cast<F *>(bins + nbin) + wave * CSR_CAP;    // [CSR_CAP] per wave, 16-byte aligned
+    for (int j = threadIdx.x; j < nbin; j += blockDim.x) bins[j] = 0.0;
     __syncthreads();
     const int64_t nchunk = ceil_div_dev(n, (int64_t)CSR_RPW);
     const int64_t cb = ((int64_t)blockIdx.x * CSR_WAVES + wave) * chunks_per_wave;
@@ -335,11 +340,21 @@ __global__ __launch_bounds__(CSR_WAVES * 64) void csr_rmatvec_stream_kernel(
                 // (slots in front of the chunk's first entry and behind the tile's last were not written: skipped)
                 if (e >= first && e < cnt) {
                     const F x = t.x[2 * k];
-                    atomic_add(&bins[t.col(2 * k)], (lds_acc_t)((square ? x * x : x) * vv[0]));
+                    if constexpr (MOM == 2) {
+                        atomic_add(&bins[t.col(2 * k)], (lds_acc_t)(x * vv[0]));
+                        atomic_add(&bins2[t.col(2 * k)], (lds_acc_t)(x * x * vv[0]));
+                    } else {
+                        atomic_add(&bins[t.col(2 * k)], (lds_acc_t)((square ? x * x : x) * vv[0]));
+                    }
                 }
                 if (e + 1 >= first && e + 1 < cnt) {
                     const F x = t.x[2 * k + 1];
-                    atomic_add(&bins[t.col(2 * k + 1)], (lds_acc_t)((square ? x * x : x) * vv[1]));
+                    if constexpr (MOM == 2) {
+                        atomic_add(&bins[t.col(2 * k + 1)], (lds_acc_t)(x * vv[1]));
+                        atomic_add(&bins2[t.col(2 * k + 1)], (lds_acc_t)(x * x * vv[1]));
+                    } else {
+                        atomic_add(&bins[t.col(2 * k + 1)], (lds_acc_t)((square ? x * x : x) * vv[1]));
+                    }
                 }
             }
             __builtin_amdgcn_wave_barrier();
@@ -348,6 +363,10 @@ __global__ __launch_bounds__(CSR_WAVES * 64) void csr_rmatvec_stream_kernel(
     __syncthreads();
     F *dst = ws + (int64_t)blockIdx.x * m;
     for (int j = threadIdx.x; j < m; j += blockDim.x) dst[j] = (F)bins[j];
+    if constexpr (MOM == 2) {
+        F *dst2 = ws + ((int64_t)gridDim.x + blockIdx.x) * m;
+        for (int j = threadIdx.x; j < m; j += blockDim.x) dst2[j] = (F)bins2[j];
+    }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1058,6 +1077,46 @@ static int run_csr_rmatvec_u16(const F *data, const uint16_t *ind16, const int64
     return launch_reduce_partials<F>(ws, m, (int)nblk, 1, out, m, true, st);
 }
 
+// s2[j] += sum_i dm[i] X[i, j]^2 and, when s1 is given, s1[j] += sum_i dm[i] X[i, j] from the same read of every
+// entry (the diagonal of X' diag(dm) X and the first moment StandardizedMatrix centres it with).
+template <typename F, typename IDX>
+static int run_csr_sandwich_diag(const F *data, const IDX *ind, const int64_t *ptr, int64_t n, int64_t m,
+                                 const F *dm, F *s1, F *s2, hipStream_t st) {
+    TM_REQUIRE(n >= 0 && m >= 0, "negative shape");
+    if (n == 0 || m == 0) return TM_OK;
+    TM_REQUIRE(data && ind && ptr && dm && s2, "data, indices, indptr, dm and s2 are required");
+    const int nmom = s1 ? 2 : 1;
+    const size_t mp = (size_t)((m + 1) & ~(int64_t)1);
+    const size_t lds = sizeof(lds_acc_t) * mp * nmom + sizeof(F) * (size_t)(CSR_WAVES * CSR_CAP);
+    TM_REQUIRE(lds <= SP_LDS_MAX, "csr_sandwich_diag: the accumulators must fit the LDS");
+    TM_REQUIRE(sizeof(IDX) == 4 || m <= 65536, "csr_sandwich_diag (16-bit columns): at most 65536 columns");
+    const uintptr_t dpa = reinterpret_cast<uintptr_t>(data), ipa = reinterpret_cast<uintptr_t>(ind);
+    TM_REQUIRE(dpa % sizeof(F) == 0 && ipa % sizeof(IDX) == 0 &&
+                   ((dpa / sizeof(F)) & 1) == ((ipa / sizeof(IDX)) & 1),
+               "csr_sandwich_diag: values and columns must start at entries of the same parity");
+    auto kern = s1 ? &csr_rmatvec_stream_kernel<F, IDX, 2> : &csr_rmatvec_stream_kernel<F, IDX, 1>;
+    if (lds > 48 * 1024)
+        TM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int64_t nchunk = ceil_div(n, CSR_RPW);
+    const int64_t nwave = std::min<int64_t>(nchunk, (int64_t)NUM_CU * 4 * CSR_WAVES);
+    const int64_t cpw = ceil_div(nchunk, nwave);
+    const int64_t nblk = ceil_div(ceil_div(nchunk, cpw), CSR_WAVES);
+    void *wsv = nullptr;
+    int rc = get_workspace(sizeof(F) * (size_t)(nmom * nblk * m) + 256, &wsv, st);
+    if (rc) return rc;
+    F *ws = reinterpret_cast<F *>(wsv);
+    prof_begin(st);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(CSR_WAVES * 64), lds, st, data, ind, ptr, dm, n, (int)m, cpw,
+                       ws, 1);
+    prof_end(st);
+    TM_LAUNCH_CHECK();
+    if (!s1) return launch_reduce_partials<F>(ws, m, (int)nblk, 1, s2, m, true, st);
+    rc = launch_reduce_partials<F>(ws, m, (int)nblk, 1, s1, m, true, st);
+    if (rc) return rc;
+    return launch_reduce_partials<F>(ws + nblk * m, m, (int)nblk, 1, s2, m, true, st);
+}
+
 template <typename F>
 static int run_csr_rmatvec(const F *data, const int32_t *ind, const int64_t *ptr, int64_t n,
                            int64_t m, const F *v, const int32_t *rows, int64_t n_rows,
@@ -1399,6 +1458,24 @@ int tm_csr_col_sq_f64(const double *csr_data, const int32_t *csr_indices,
                       double *out, void *stream) {
     return run_csr_rmatvec<double>(csr_data, csr_indices, csr_indptr, n, m, w, nullptr, 0, nullptr,
                                    0, out, as_stream(stream), 1);
+}
+
+/* K7b: both weighted column moments of the CSR twin from one pass (see include/tabmat_hip.h) */
+int tm_csr_sandwich_diag_u16_f32(const float *data, const uint16_t *ind16, const int64_t *ptr, int64_t n, int64_t m,
+                                 const float *dm, float *s1, float *s2, void *stream) {
+    return run_csr_sandwich_diag<float, uint16_t>(data, ind16, ptr, n, m, dm, s1, s2, as_stream(stream));
+}
+int tm_csr_sandwich_diag_u16_f64(const double *data, const uint16_t *ind16, const int64_t *ptr, int64_t n, int64_t m,
+                                 const double *dm, double *s1, double *s2, void *stream) {
+    return run_csr_sandwich_diag<double, uint16_t>(data, ind16, ptr, n, m, dm, s1, s2, as_stream(stream));
+}
+int tm_csr_sandwich_diag_f32(const float *data, const int32_t *ind, const int64_t *ptr, int64_t n, int64_t m,
+                             const float *dm, float *s1, float *s2, void *stream) {
+    return run_csr_sandwich_diag<float, int32_t>(data, ind, ptr, n, m, dm, s1, s2, as_stream(stream));
+}
+int tm_csr_sandwich_diag_f64(const double *data, const int32_t *ind, const int64_t *ptr, int64_t n, int64_t m,
+                             const double *dm, double *s1, double *s2, void *stream) {
+    return run_csr_sandwich_diag<double, int32_t>(data, ind, ptr, n, m, dm, s1, s2, as_stream(stream));
 }
 
 int tm_csr_dense_sandwich_f32(const float *csr_data, const int32_t *csr_indices,

@@ -415,6 +415,39 @@ class DenseMatrix(MatrixBase):
             g = g[D.idx_dev(a.cols, torch.int64)]
         return a.finish(g)
 
+    def _sdiag_dev(self, d, rows, center=None):
+        """out[j] = sum_{r in rows} d[r] (x_rj - center_j)^2 over ALL columns (device, the block dtype).  d: device
+        vector over all rows; rows: int32 device tensor or None; center: device vector of the block dtype or
+        None.  One pass of tm_dense_sandwich_diag_* over the row-major block (an F-ordered block through its
+        twin) with the excluded rows at d = 0; blocks the kernel does not take (no twin, too wide) run
+        tm_dense_col_sq_dev_* on the same masked d.  A row restriction on a block holding inf / nan reads the
+        selected rows only (gathered first): 0 * inf of an excluded row would leak a NaN."""
+        if rows is not None and not self._values_finite():
+            r64 = rows.to(torch.int64)
+            sub = self._dev().as_2d()[r64].contiguous()
+            return DenseMatrix(sub)._sdiag_dev(d[r64].contiguous(), None, center)
+        dm = D.masked_d(d, rows).contiguous()
+        blk = self._smv_block()
+        if blk is not None:
+            return xd.dense_sandwich_diag(blk, dm, center)
+        shift = torch.zeros((self.shape[1],), dtype=dm.dtype, device=dm.device) if center is None else center
+        return xd.transpose_square_dot_weights(self._dev(), dm, shift)
+
+    def sandwich_diag(self, d, rows=None, cols=None):
+        """diag(sandwich(d, rows, cols)) without forming the sandwich (MatrixBase.sandwich_diag): ONE pass over
+        the block (_sdiag_dev); a column restriction selects from the length-m result (an entry depends on its
+        own column only)."""
+        from .matrix_base import _sd_args
+
+        a = _sd_args(self, d, rows, cols)
+        if a.trivial is not None:
+            return a.finish(a.trivial)
+        tdt = D.torch_dtype(self.dtype)
+        g = self._sdiag_dev(D.to_dev(a.d, tdt), D.idx_dev(a.rows))
+        if a.cols is not None:
+            g = g[D.idx_dev(a.cols, torch.int64)]
+        return a.finish(g)
+
     def sandwich(self, d, rows=None, cols=None):
         """X[rows, cols].T @ diag(d[rows]) @ X[rows, cols] (dense_matrix.py:153-163)."""
         on_dev = D.is_dev(d)

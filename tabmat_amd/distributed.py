@@ -73,6 +73,7 @@ class RowShardedMatrix:
                  local_transpose_matvec: Optional[Callable] = None,
                  local_sandwich_and_transpose_matvec: Optional[Callable] = None,
                  local_sandwich_matvec: Optional[Callable] = None,
+                 local_sandwich_diag: Optional[Callable] = None,
                  bounds: Optional[tuple] = None, n_global: Optional[int] = None,
                  always_reduce: bool = False):
         self.local = local
@@ -91,6 +92,7 @@ class RowShardedMatrix:
         else:             # (only the separate products were injected: they make the pair)
             self._both = lambda d, v, rows, cols: (self._sandwich(d, rows, cols), self._tmv(v, rows, cols))
         self._smv = local_sandwich_matvec or (lambda d, u, rows, cols: local.sandwich_matvec(d, u, rows, cols))
+        self._sdiag = local_sandwich_diag or (lambda d, rows, cols: local.sandwich_diag(d, rows, cols))
         self.shape = local.shape
         self.dtype = local.dtype
 
@@ -181,6 +183,16 @@ class RowShardedMatrix:
         """d: global length-n vector; rows: global row ids or None; u: replicated."""
         lo, hi = self.bounds
         return self.sandwich_matvec(self.local_slice(d), u, bucket_rows(rows, lo, hi), cols)
+
+    def sandwich_diag(self, d, rows=None, cols=None):
+        """diag(sandwich(d, rows, cols)) of the whole matrix: the local diagonal (rows LOCAL ids) and ONE
+        all-reduce of the length-k result."""
+        return self._all_reduce(self._sdiag(d, rows, cols))
+
+    def sandwich_diag_global(self, d, rows=None, cols=None):
+        """d: global length-n vector; rows: global row ids or None."""
+        lo, hi = self.bounds
+        return self.sandwich_diag(self.local_slice(d), bucket_rows(rows, lo, hi), cols)
 
     def matvec(self, v, cols=None, out=None):
         """Row-partitioned output: the local rows of X v; no collective."""

@@ -265,3 +265,17 @@ def dense_sandwich_matvec(X: DenseDev, u, dm, t_add=None, center=None, shift=Non
     call(f"tm_dense_sandwich_matvec_{D.fsuf(X.buf)}", D.p(X.buf), X.n, X.m, D.p(u), D.p(dm), D.p(t_add),
          D.p(center), D.p(shift), D.p(g), D.p(w), D.stream_ptr())
     return g, w
+
+
+def dense_sandwich_diag(X: DenseDev, dm, center=None):
+    """out[j] = sum_r dm[r] (X[r, j] - center[j])^2 from ONE pass over a C-ordered block (tm_dense_sandwich_diag_*:
+    the diagonal of the product tm_dense_sandwich_matvec_* applies; same blocks, sandwich_matvec_supported).
+    dm: length X.n, center: length X.m or None, both of the block's dtype."""
+    out = D.out_buf((X.m,), X.dtype)
+    D.same_float("dense_sandwich_diag", X.buf, dm, center)
+    assert sandwich_matvec_supported(X)
+    assert dm.numel() == X.n and dm.is_contiguous()
+    assert center is None or (center.numel() == X.m and center.is_contiguous())
+    call(f"tm_dense_sandwich_diag_{D.fsuf(X.buf)}", D.p(X.buf), X.n, X.m, D.p(dm), D.p(center), D.p(out),
+         D.stream_ptr())
+    return out

@@ -439,3 +439,41 @@ def csc_densify_cols(rows, vals, seg, tcol, max_len, T):
     D.same_float("csc_densify_cols", vals, T)
     call(f"tm_csc_densify_cols_{D.fsuf(T)}", D.p(rows), D.p(vals), D.p(seg), D.p(tcol),
          int(tcol.numel()), int(max_len), D.p(T), T.shape[1], D.stream_ptr())
+
+
+def csr_sandwich_diag_supported(A: CsrDev, want_s1: bool, u16: bool) -> bool:
+    """True when tm_csr_sandwich_diag_* takes the block: its LDS bins fit (two arrays with want_s1) and values and
+    columns start at entries of the same parity (include/tabmat_hip.h)."""
+    isz = A.data.element_size()
+    ind = A._ind16 if u16 else A._ind32
+    if ind is None or (u16 and A.m > 65536):
+        return False
+    bins = 8 * (2 if want_s1 else 1) * ((A.m + 1) & ~1) + isz * 4096
+    return (bins <= 128 * 1024
+            and (A.data.data_ptr() // isz) % 2 == (ind.data_ptr() // ind.element_size()) % 2)
+
+
+def csr_sandwich_diag(A: CsrDev, dm, want_s1=False):
+    """(s1 or None, s2) with s1[j] = sum_i dm[i] A[i, j] and s2[j] = sum_i dm[i] A[i, j]^2 over all rows and columns
+    (dm: weights with the excluded rows at 0) from ONE pass over the CSR twin (tm_csr_sandwich_diag_*): on the
+    resident 16-bit column twin when the block has one (nothing is widened), the int32 columns otherwise.  A block
+    the kernel does not take (more columns than its LDS bins hold, a row view of odd parity) gets the two
+    single-moment launches, tm_csr_rmatvec_* and tm_csr_col_sq_*."""
+    s2 = D.zeros((A.m,), A.dtype)
+    s1 = D.zeros((A.m,), A.dtype) if want_s1 else None
+    if A.n == 0 or A.m == 0 or A.data.numel() == 0:
+        return s1, s2
+    D.same_float("csr_sandwich_diag", A.data, dm)
+    assert dm.numel() == A.n and dm.is_contiguous()
+    suf = D.fsuf(A.data)
+    for u16 in (True, False):
+        if csr_sandwich_diag_supported(A, want_s1, u16):
+            ind = A._ind16 if u16 else A._ind32
+            call(f"tm_csr_sandwich_diag_{'u16_' if u16 else ''}{suf}", D.p(A.data), D.p(ind), D.p(A.indptr), A.n, A.m,
+                 D.p(dm), D.p(s1), D.p(s2), D.stream_ptr())
+            return s1, s2
+    if want_s1:
+        csc_rmatvec(A, dm, None, None, out=s1)
+    call(f"tm_csr_col_sq_{suf}", D.p(A.data), D.p(A.indices), D.p(A.indptr), A.n, A.m, D.p(dm), D.p(s2),
+         D.stream_ptr())
+    return s1, s2

@@ -50,6 +50,18 @@ class MatrixBase(ABC):
             return a.finish(a.trivial)
         return a.finish(_smv_compose(self, a))
 
+    def sandwich_diag(self, d, rows=None, cols=None):
+        """The diagonal of sandwich(d, rows, cols) -- out[q] = sum_{i in rows} d[i] self[i, cols[q]]^2 -- without
+        forming the (k, k) sandwich (a Jacobi preconditioner for sandwich_matvec; a repeated row id counts once
+        per occurrence, a repeated column id repeats its entry).  1-D of length k = len(cols) (all columns when
+        None): numpy for a numpy d, a device tensor for a device d, in the dtype of sandwich(d, rows, cols).
+        This default is correct but slow (one getcol and one transpose_matvec per selected column); every class
+        of the package overrides it with a one-pass path."""
+        a = _sd_args(self, d, rows, cols)
+        if a.trivial is not None:
+            return a.finish(a.trivial)
+        return _sd_compose(self, a)
+
     @abstractmethod
     def getcol(self, i: int):
         ...
@@ -234,3 +246,41 @@ def _smv_compose(mat, a):
     t = mat.matvec(a.u_full(tdt), cols=a.cols)
     w = D.to_dev(a.d, tdt) * t
     return mat.transpose_matvec(w, rows=a.rows, cols=a.cols)
+
+
+def _sd_args(mat, d, rows, cols, h_dtype=None):
+    """Host-side checks of sandwich_diag (no device work), as sandwich makes them: check_sandwich_compatible and
+    normalize_index.  h_dtype: the dtype sandwich() returns (default: the matrix dtype).  .trivial is the result
+    (a device tensor) when rows or cols are empty, else None."""
+    from . import _device as D
+    from .util import check_sandwich_compatible, normalize_index
+
+    on_dev = D.is_dev(d)
+    if not on_dev:
+        d = np.asarray(d)
+    check_sandwich_compatible(mat, d)
+    if d.ndim != 1:
+        raise ValueError("sandwich_diag needs a 1-D weight vector")
+    n, p = mat.shape
+    rows_n = normalize_index(rows, n)
+    cols_n = normalize_index(cols, p)
+    k = p if cols_n is None else len(cols_n)
+    out_dtype = np.dtype(h_dtype if h_dtype is not None else mat.dtype)
+    trivial = None
+    if k == 0 or (rows_n is not None and len(rows_n) == 0):
+        trivial = D.zeros((k,), D.torch_dtype(out_dtype))
+    return _SmvArgs(mat=mat, d=d, u=None, rows=rows_n, cols=cols_n, n=n, p=p, k=k, on_dev=on_dev,
+                    out_dtype=out_dtype, trivial=trivial)
+
+
+def _sd_compose(mat, a):
+    """sandwich_diag column by column from getcol and transpose_matvec (the MatrixBase default)."""
+    from . import _device as D
+
+    d = D.to_host(a.d) if a.on_dev else a.d
+    cols = range(a.p) if a.cols is None else a.cols.tolist()
+    out = np.empty(a.k, dtype=a.out_dtype)
+    for q, j in enumerate(cols):
+        x = np.asarray(mat.getcol(int(j)).toarray(), dtype=d.dtype).reshape(-1)
+        out[q] = np.asarray(mat.transpose_matvec(d * x, rows=a.rows, cols=[int(j)])).reshape(-1)[0]
+    return D.to_dev(out, D.torch_dtype(a.out_dtype)) if a.on_dev else out

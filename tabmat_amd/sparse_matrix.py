@@ -456,6 +456,49 @@ class SparseMatrix(MatrixBase):
             full = full.index_select(0, inv).index_select(1, inv)
         return full
 
+    def _sdiag_dev(self, d, rows, want_s1=False):
+        """(s1 or None, s2) over ALL columns (device, the block dtype): s2[j] = sum_{r in rows} d[r] x_rj^2, the
+        diagonal of the sandwich, and with want_s1 the first moment s1[j] = sum_{r in rows} d[r] x_rj, both from
+        one pass over the CSR twin (tm_csr_sandwich_diag_*: the 16-bit column twin when the block holds one).
+        d: device vector over all rows; rows: int32 device tensor or None (a masked d; a block holding inf / nan
+        gets the selected rows gathered first).  Row parts are summed."""
+        parts = self._row_parts()
+        if parts is not None:
+            s1 = D.zeros((self.shape[1],), d.dtype) if want_s1 else None
+            s2 = D.zeros((self.shape[1],), d.dtype)
+            for a, b, part in parts:
+                r = None
+                if rows is not None:
+                    r64 = rows.to(torch.int64)
+                    sel = r64[(r64 >= a) & (r64 < b)]
+                    if sel.numel() == 0:
+                        continue
+                    r = (sel - a).to(torch.int32)
+                p1, p2 = part._sdiag_dev(d[a:b], r, want_s1)
+                s2 += p2
+                if want_s1:
+                    s1 += p1
+            return s1, s2
+        A = self._dev()
+        if rows is not None and A.data.numel() > 0 and not self._values_finite():
+            r64 = rows.to(torch.int64)
+            return xs.csr_sandwich_diag(A.take_rows("index", r64), d[r64].contiguous(), want_s1)
+        return xs.csr_sandwich_diag(A, D.masked_d(d, rows).contiguous(), want_s1)
+
+    def sandwich_diag(self, d, rows=None, cols=None):
+        """diag(sandwich(d, rows, cols)) without forming the sandwich (MatrixBase.sandwich_diag): one pass over
+        the CSR twin (_sdiag_dev), a column restriction selects from the length-m result."""
+        from .matrix_base import _sd_args
+
+        a = _sd_args(self, d, rows, cols)
+        if a.trivial is not None:
+            return a.finish(a.trivial)
+        tdt = D.torch_dtype(self.dtype)
+        _, g = self._sdiag_dev(D.to_dev(a.d, tdt), D.idx_dev(a.rows))
+        if a.cols is not None:
+            g = g[D.idx_dev(a.cols, torch.int64)]
+        return a.finish(g)
+
     def sandwich(self, d, rows=None, cols=None):
         """sparse_matrix.py:175-185."""
         on_dev = D.is_dev(d)

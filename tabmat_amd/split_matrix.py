@@ -151,6 +151,25 @@ def _merge_same_kind(matrices, indices):
     return matrices, indices
 
 
+def _block_sdiag(mb, d, rows, center=None, want_s1=False):
+    """(s2, s1 or None) of one block over all of its columns, device vectors: s2[j] = sum_{r in rows} d[r] x_rj^2
+    (a dense block with `center`: of x - center) and, for sparse and categorical blocks with want_s1,
+    s1[j] = sum_{r in rows} d[r] x_rj.  d: device vector over all rows; rows: int32 device tensor or None."""
+    d = d.to(D.torch_dtype(mb.dtype))
+    if isinstance(mb, DenseMatrix):
+        return mb._sdiag_dev(d, rows, None if center is None else center.to(d.dtype).contiguous()), None
+    if isinstance(mb, SparseMatrix):
+        s1, s2 = mb._sdiag_dev(d, rows, want_s1)
+        return s2, s1
+    if isinstance(mb, CategoricalMatrix):
+        h = mb._sandwich_diag_dev(d, rows, None)       # one-hot entries are 0 / 1: both moments are the histogram
+        return h, (h if want_s1 else None)
+    # any other MatrixBase: its public products
+    r = None if rows is None else D.to_host(rows)
+    s2 = D.to_dev(mb.sandwich_diag(d, r))
+    return s2, (D.to_dev(mb.transpose_matvec(d, r)) if want_s1 else None)
+
+
 class SplitMatrix(MatrixBase):
     """matrices: the blocks; indices: for each block the (sorted) global columns it covers."""
 
@@ -1019,6 +1038,63 @@ class SplitMatrix(MatrixBase):
         if res is None:
             return a.finish(_smv_compose(self, a))
         g = res[0]
+        if a.cols is not None:
+            g = g[self._cols_dev64(a.cols)]
+        return a.finish(g)
+
+    def _sdiag_dev(self, d, rows, cols_host=None, centers=None, want_s1=False):
+        """(s2, s1 or None) over ALL p columns, float64 on the device: s2[j] = sum_{r in rows} d[r] x_rj^2 -- the
+        diagonal of the sandwich -- and with want_s1 the first moments s1[j] = sum_{r in rows} d[r] x_rj of the
+        sparse and categorical columns (what StandardizedMatrix.sandwich_diag expands their centred squares
+        from; 0 for dense columns).  One product per block (_block_sdiag), scattered to `indices`; a block
+        without a column in cols_host launches nothing (its entries stay 0).  centers: {block: column centres
+        of a dense block, the block dtype}: that block's s2 is sum d (x - c)^2, the centre taken inside the
+        kernel.  d: device vector over all rows; rows: int32 device tensor or None.  Row parts are summed."""
+        p = self.shape[1]
+        parts = self._parts()
+        if parts is not None:
+            s2 = D.zeros((p,), torch.float64)
+            s1 = D.zeros((p,), torch.float64) if want_s1 else None
+            for a, b, part in parts:
+                r = None
+                if rows is not None:
+                    r64 = rows.to(torch.int64)
+                    sel = r64[(r64 >= a) & (r64 < b)]
+                    if sel.numel() == 0:
+                        continue
+                    r = (sel - a).to(torch.int32)
+                p2, p1 = part._sdiag_dev(d[a:b], r, cols_host, centers, want_s1)
+                s2 += p2
+                if want_s1:
+                    s1 += p1
+            return s2, s1
+        mask = None
+        if cols_host is not None:
+            mask = np.zeros(p, dtype=bool)
+            mask[np.asarray(cols_host, dtype=np.int64)] = True
+        s2 = D.zeros((p,), torch.float64)
+        s1 = D.zeros((p,), torch.float64) if want_s1 else None
+        idx_d = self._full_dev_indices()
+        for b, (mb, idx) in enumerate(zip(self.matrices, self.indices)):
+            if mb.shape[0] == 0 or (mask is not None and not mask[idx].any()):
+                continue
+            r2, r1 = _block_sdiag(mb, d, rows, None if centers is None else centers.get(b), want_s1)
+            s2[idx_d[b]] = r2.to(torch.float64)
+            if want_s1 and r1 is not None:
+                s1[idx_d[b]] = r1.to(torch.float64)
+        return s2, s1
+
+    def sandwich_diag(self, d, rows=None, cols=None):
+        """diag(sandwich(d, rows, cols)) without forming the (k, k) sandwich (MatrixBase.sandwich_diag), float64
+        like the sandwich.  Every block with a selected column is read once -- the dense block by
+        tm_dense_sandwich_diag_*, the sparse block by tm_csr_sandwich_diag_*, a categorical block by its
+        histogram -- and nothing larger than a length-p vector is allocated."""
+        from .matrix_base import _sd_args
+
+        a = _sd_args(self, d, rows, cols, h_dtype=np.float64)
+        if a.trivial is not None:
+            return a.finish(a.trivial)
+        g, _ = self._sdiag_dev(D.to_dev(a.d, D.torch_dtype(self.dtype)), D.idx_dev(a.rows), a.cols)
         if a.cols is not None:
             g = g[self._cols_dev64(a.cols)]
         return a.finish(g)

@@ -280,6 +280,77 @@ class StandardizedMatrix:
             g = g[D.idx_dev(a.cols, torch.int64)]
         return a.finish(g)
 
+    def _diag_centering(self):
+        """(delta, dense mask, {block: centres}) for sandwich_diag, cached.  A dense column j is read as
+        x_j - c_j with c_j = -shift_j / mult_j inside the kernel (both data types), so self[:, j] =
+        mult_j (x_j - c_j) + delta_j: delta_j is 0 -- up to the rounding of c_j -- unless mult_j = 0 (c_j is set
+        to 0 there and delta_j = shift_j).  The mask (bool device vector over the p columns) marks the dense
+        columns; blocks whose centres are all zero are left out of the dict."""
+        hit = self._dev_cache.get("diag_centering")
+        if hit is not None:
+            return hit
+        from .dense_matrix import DenseMatrix
+        from .split_matrix import SplitMatrix
+
+        mat, p = self.mat, self.shape[1]
+        if isinstance(mat, SplitMatrix):
+            blocks = [(b, mb, idx) for b, (mb, idx) in enumerate(zip(mat.matrices, mat.indices))
+                      if isinstance(mb, DenseMatrix)]
+        elif isinstance(mat, DenseMatrix):
+            blocks = [(0, mat, np.arange(p))]
+        else:
+            blocks = []
+        with np.errstate(all="ignore"):
+            c_all = -self.shift if self.mult is None else -self.shift / self.mult
+        bad = ~np.isfinite(c_all)
+        c_all = np.where(bad, 0.0, c_all)
+        delta = np.where(bad, self.shift, 0.0).astype(np.float64)
+        mask = np.zeros(p, dtype=bool)
+        vec = {}
+        for b, mb, idx in blocks:
+            mask[idx] = True
+            cb = np.ascontiguousarray(c_all[idx], dtype=np.float64)
+            if np.any(cb != 0.0):
+                vec[b] = D.to_dev(cb, D.torch_dtype(mb.dtype))
+        hit = self._dev_cache["diag_centering"] = (D.to_dev(delta, torch.float64), D.to_dev(mask), vec)
+        return hit
+
+    def sandwich_diag(self, d, rows=None, cols=None):
+        """diag(sandwich(d, rows, cols)) without forming the sandwich, float64: with self[:, j] = mult_j x_j +
+        shift_j the entry is sum_r d_r (mult_j x_rj + shift_j)^2.  Dense columns: mult_j^2 sum_r d_r (x_rj - c_j)^2,
+        the centre c_j = -shift_j / mult_j subtracted inside tm_dense_sandwich_diag_* (nothing of size
+        (mean / std)^2 cancels).  Sparse and categorical columns: mult_j^2 s2_j + 2 mult_j shift_j s1_j +
+        shift_j^2 sum(d[rows]) from the two moments of one pass (tm_csr_sandwich_diag_*; the histogram is both
+        moments of a categorical block)."""
+        from .matrix_base import _sd_args
+        from .split_matrix import SplitMatrix, _block_sdiag
+
+        a = _sd_args(self, d, rows, cols, h_dtype=np.float64)
+        if a.trivial is not None:
+            return a.finish(a.trivial)
+        d_dev = D.to_dev(a.d, D.torch_dtype(self.dtype))
+        rows_d = D.idx_dev(a.rows)
+        delta, dense, centers = self._diag_centering()
+        want_s1 = bool(np.any(self.shift != 0.0))
+        if isinstance(self.mat, SplitMatrix):
+            s2, s1 = self.mat._sdiag_dev(d_dev, rows_d, a.cols, centers, want_s1)
+        else:
+            s2, s1 = _block_sdiag(self.mat, d_dev, rows_d, centers.get(0), want_s1)
+            s2 = s2.to(torch.float64)
+            s1 = None if s1 is None else s1.to(torch.float64)
+        shift = self._shift_dev()
+        mult = self._mult_dev()
+        g = s2 if mult is None else s2 * mult * mult
+        if want_s1:
+            sum_d = _vec_sum(d_dev, rows_d)
+            if s1 is None:
+                s1 = torch.zeros_like(s2)
+            cross = 2.0 * shift * s1 if mult is None else 2.0 * mult * shift * s1
+            g = g + torch.where(dense, delta * delta * sum_d, cross + shift * shift * sum_d)
+        if a.cols is not None:
+            g = g[D.idx_dev(a.cols, torch.int64)]
+        return a.finish(g)
+
     def unstandardize(self) -> MatrixBase:
         return self.mat
 
