@@ -489,9 +489,13 @@ int tm_csr_dense_sandwich_lgc_f64(const double *cvals, const uint32_t *cmap, con
  *   vals F[16 * batches + 192]        value (192 slots of slack at the end are read, not used: zeros)
  *   meta uint16[16 * batches + 192]   (slab & 63) << 10 | row in slab << 4 | column in group   (round 6; a uint32
  *                                     row << 4 | column before: 12 -> 10 bytes per slot).  The kernels rebuild a
- *                                     slot's slab from the 6-bit tag and a running slab, so two consecutive batches of
- *                                     a group must lie fewer than 64 slabs apart: the builder gives an EMPTY block one
- *                                     padding batch (value 0, row = the slab's first row) at every 32nd slab.
+ *                                     slot's slab from the 6-bit tag and a running slab that all 64 slots of a step
+ *                                     (four batches) share and that is the slab of the step's last slot afterwards.
+ *                                     THE CALLER'S CONTRACT: for every group and every slab s0, the first four batches
+ *                                     at or after s0 lie in [s0, s0 + 63], and any five consecutive batches span at
+ *                                     most 63 slabs.  The builder gives an EMPTY block one padding batch (value 0,
+ *                                     row = the slab's first row) at every 15th slab (4 x 15 < 64; every 16th would
+ *                                     not do).  A stream that breaks the contract gives wrong sums, not an error.
  *   bstart uint32[G][S + 1]           first batch of block (group, slab); entry S = the end of the group
  * colsum (length m, kernel column order, = A' d from the same pass; reference standardized_mat.py:149-150)
  * may be NULL.  out: (m, r), kernel column order, overwritten. */

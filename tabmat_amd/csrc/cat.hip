@@ -1162,7 +1162,10 @@ __global__ __launch_bounds__(1024) void multi_cat_sparse_ent_kernel(
             }
         };
         // (round 6: 16-bit meta words {slab & 63, row in slab, column}: the slab of a slot from the tag and a running
-        // slab, in stream order -- load_rows is called step after step; rows of slots behind the wave's stream clamped)
+        // slab, in stream order -- load_rows is called step after step; rows of slots behind the wave's stream clamped.
+        // All 64 lanes of a sub-step use ONE running slab, replaced by lane 63's slab afterwards: right because the
+        // builder keeps any five consecutive batches of a group, and the first four at or after any slab sa, within 63
+        // slabs -- SlabEnt.CONT_PERIOD, tests/test_ent_stream_ranges.py)
         unsigned cur_slab = (unsigned)sa;
         const unsigned row_max = (unsigned)(n - 1);
         auto load_rows = [&](Step &t) {
@@ -1401,6 +1404,9 @@ __global__ __launch_bounds__(1024) void multi_cat_sparse_rows_kernel(
     const int nel = cs.total * tstr;
     for (int b = threadIdx.x; b < nel; b += blockDim.x) tile[b] = 0.0;
     __syncthreads();
+    // (the u8 column twin counts from its chunk's first column: `g >> 2` and `g & 3` below are group / chunk and
+    // group % chunk only while a chunk holds exactly four groups)
+    static_assert(SPARSE_CHUNK_COLS == 4 * GC, "the chunk of the chunk-major twin must hold four 32-column groups");
     const int g = blockIdx.y;                    // 32-column group; chunk = g / 4
     const int ch = g >> 2;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;

@@ -13,6 +13,7 @@ namespace tmh {
 constexpr int WAVE = 64;           // CDNA wavefront
 constexpr int NUM_CU = 256;        // MI355X
 constexpr int NUM_XCD = 8;
+constexpr int SPARSE_CHUNK_COLS = 128;   // columns per chunk of the chunk-major CSR twin (tm_sparse_chunk_cols)
 constexpr size_t LDS_BYTES = 160 * 1024;
 
 void set_error(const char *fmt, ...);

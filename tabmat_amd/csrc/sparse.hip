@@ -2401,7 +2401,7 @@ static int run_csr_dense_ellw(const F *vals, const unsigned *koff, const int64_t
 
 extern "C" {
 
-int tm_sparse_chunk_cols(void) { return 128; }
+int tm_sparse_chunk_cols(void) { return tmh::SPARSE_CHUNK_COLS; }
 int tm_sparse_sandwich_chunked_f32(const float *csr_data, const int32_t *csr_indices,
                                    const int32_t *cptr, int64_t n, int64_t m, int64_t nnz,
                                    const float *d, float *out, void *stream) {

@@ -25,8 +25,9 @@
 // one another, slab after slab, so a wave walks ONE contiguous stream:
 //     vals F[T]              value
 //     meta uint16[T]         (slab & 63) << 10 | row in slab << 4 | column in group   (round 6; uint32 row << 4 | column
-//                            before: 12 -> 10 bytes per slot.  An empty block at every 32nd slab holds one padding batch,
-//                            so that two batches of a group are never 64 slabs apart and the 6-bit tag is unambiguous.)
+//                            before: 12 -> 10 bytes per slot.  An empty block at every 15th slab holds one padding batch,
+//                            so that any FIVE consecutive batches of a group -- what one superbatch and the last batch of
+//                            the one before cover -- span at most 63 slabs and the 6-bit tag is unambiguous.)
 //     bstart uint32[G][S+1]  first batch of block (group, slab); entry S = the end of the group's stream
 // 10 bytes per slot.  A wave takes its stream in SUPERBATCHES of 64 slots, lane <-> slot: one coalesced load
 // of the values and one of the meta words a whole superbatch (~5000 cycles) ahead, the d of every slot's row
@@ -257,8 +258,11 @@ __global__ __launch_bounds__(EN_THREADS) __attribute__((amdgpu_num_vgpr(EN_CVGPR
         en_load_stream<F>(lane_v, vbase + (int64_t)k * EN_SB, lane_m, mbase + (int64_t)k * EN_SB);
     };
     // The stream's meta word is 16 bits {slab & 63, row in slab, column in group}; the slot's slab is rebuilt from the
-    // 6-bit tag and a wave-uniform running slab (the stream is ordered by slab and the builder leaves no gap of 64 slabs
-    // between two batches of a group): my = row << 4 | column as before round 6, row = slab * 64 + row in slab.
+    // 6-bit tag and a wave-uniform running slab: all 64 slots of a superbatch against the slab of the LAST slot of the
+    // superbatch before (s0 at the start).  The stream is ordered by slab, and the builder keeps any five consecutive
+    // batches of a group, and the first four at or after any slab s0, within 63 slabs (SlabEnt.CONT_PERIOD; the decode
+    // is modelled and the invariant tested in tests/test_ent_stream_ranges.py): my = row << 4 | column as before
+    // round 6, row = slab * 64 + row in slab.
     const unsigned s0u = (unsigned)s0;
     unsigned cur_slab = s0u;
     auto expand = [&](unsigned m16) -> unsigned {

@@ -843,7 +843,8 @@ int run_syrk_i8_panel(const double *X, int64_t ldx, int64_t n, int64_t m, const 
     const int64_t n_items64 = ceil_div(n, I8_ITEM_ROWS);
     TM_REQUIRE(n_items64 < (1ll << 31), "too many rows");
     const int n_items = (int)n_items64;
-    const int grid = (int)std::min<int64_t>(n_items, tune("i8_grid", NUM_CU));
+    // (the knob below 1 means one workgroup: a grid of 0 cannot be launched)
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(n_items, tune("i8_grid", NUM_CU)));
     const size_t part_bytes = sizeof(double) * (size_t)grid * I8_T * 256;
     // one workspace for both kernels: [this kernel's region | the f64 kernel's region]
     const size_t own_bytes = (4096 + part_bytes + 255) / 256 * 256;

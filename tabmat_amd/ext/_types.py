@@ -819,7 +819,10 @@ class SlabEnt:
     batches of 16 slots (padding: value 0, the row of the block's first entry); blocks follow one another slab
     after slab, group after group; bstart[g, s] = first batch of the block.  10 bytes per slot (f64; 12 until
     round 5: a 32-bit row << 4 | column), 1.16 slots per nonzero at 5 % density and 512 columns.  Built once per
-    block on the device."""
+    block on the device.  The kernels rebuild a slot's slab from its 6-bit tag and a running slab shared by the 64
+    slots of a step, so for every group and every slab s0 the first four batches at or after s0 lie in
+    [s0, s0 + 63] and any five consecutive batches span at most 63 slabs: an EMPTY block at every CONT_PERIOD-th slab
+    holds one padding batch (tests/test_ent_stream_ranges.py)."""
 
     vals: torch.Tensor     # F[T + 192]
     meta: torch.Tensor     # int16[T + 192] (bit pattern of the 16-bit words)
@@ -830,6 +833,7 @@ class SlabEnt:
     mk: int                # kernel rows = G * C
 
     SLACK = 192            # slots past the end that the kernel's look-ahead loads may touch
+    CONT_PERIOD = 15       # an empty block at every 15th slab holds one padding ("continuity") batch: 4 x 15 < 64
 
     @property
     def dtype(self):
@@ -877,11 +881,14 @@ class SlabEnt:
         key = grp_of[idx64] * S + torch.div(rows, R, rounding_mode="floor")
         cnt = torch.bincount(key, minlength=G * S)
         nb = torch.div(cnt + (U - 1), U, rounding_mode="floor")
-        # round 6: the meta word carries 6 bits of the slab; an EMPTY block at every 32nd slab gets one padding batch, so
-        # that two consecutive batches of a group are never 64 slabs apart (the kernels rebuild the slab from the tag and
-        # a running slab).  Nothing is added where the blocks hold entries (BASELINE configs[3]: none).
+        # round 6: the meta word carries 6 bits of the slab; the kernels rebuild a slot's slab from the tag and a running
+        # slab that is the same for all 64 slots (four batches) of a step and is taken over from the step's LAST slot.
+        # So the five batches a step sees -- the last one of the step before and its own four -- must span at most 63
+        # slabs, wherever a range starts: an EMPTY block at every CONT_PERIOD-th slab gets one padding batch (two
+        # consecutive batches are then at most CONT_PERIOD slabs apart, five at most 4 x CONT_PERIOD = 60).  Nothing is
+        # added where the blocks hold entries (BASELINE configs[3]: none).  tests/test_ent_stream_ranges.py
         slab_of = torch.arange(G * S, device=dev, dtype=torch.int64) % S
-        nb = nb + ((cnt == 0) & (slab_of % 32 == 0)).to(nb.dtype)
+        nb = nb + ((cnt == 0) & (slab_of % SlabEnt.CONT_PERIOD == 0)).to(nb.dtype)
         total_b = int(nb.sum().item())
         if max_pad is not None and total_b * U > max_pad * nnz and total_b * U > (1 << 22):
             return None

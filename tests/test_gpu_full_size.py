@@ -221,3 +221,61 @@ def test_cfg3_categorical_50M_x_10k(zipf):
     # matvec (gather) is exact
     v = torch.rand(c, dtype=torch.float64, device="cuda", generator=g)
     assert torch.equal(X.matvec(v), v[X._dev().to(torch.int64)])
+
+
+def test_cat_sparse_gather_kernel_10M_long_wave_ranges():
+    """The gather form of categorical x sparse on the entry twin at the DEFAULT launch: a wave's range of slabs exceeds
+    the 64 the slot's 6-bit slab tag can tell apart only from about 10M rows on (2 pairs of column groups -> 128
+    workgroups x 8 waves per group over 156 250 slabs).  Entries only in the LAST slab of each wave's range, two
+    categoricals, the categorical x sparse blocks of SplitMatrix.sandwich against scipy; the sparse block's entry twin
+    is built first, so that the SplitMatrix takes the entry path without a wide dense block beside it.  (The decode
+    rule and why a continuity batch at every 32nd slab broke it: tests/test_ent_stream_ranges.py.)"""
+    import tabmat_amd as tm
+    import tabmat_amd.ext.split as xsplit_mod
+    import _ent_stream as es
+    from tabmat_amd import _lib
+
+    n, m = 10_000_000, 40
+    n_slabs = -(-n // 64)
+    n_groups = -(-m // 16)
+    n_pairs = (n_groups + 1) // 2
+    blocks = es.block_ranges(n_slabs, es.NUM_CU // n_pairs)           # run_multi_cat_sparse_ent, csrc/cat.hip
+    waves = [w for s0, s1 in blocks for w in es.wave_ranges(s0, s1, 8)]   # 16 waves, alternating between two groups
+    assert len(blocks) == 128 and len(waves) == 1024
+    assert max(b - a for a, b in waves) == 153, "the launch rule changed: this design is stale"
+    assert min(b - a for a, b in waves) > 100
+    rng = np.random.default_rng(21)
+    S = es.entries_in_slabs(n, m, [b - 1 for _, b in waves], 44, rng)
+    assert S.nnz == 1024 * 44
+    c1 = rng.integers(0, 12, n).astype(np.int32)
+    c2 = rng.integers(0, 5, n).astype(np.int32)
+    d = rng.random(n)
+    sm = tm.SparseMatrix(S.tocsc())
+    ent = sm._ent()
+    assert ent is not None
+    # (few slots per block: the launcher picks the gather kernel, the staged one starts at 44 slots per block)
+    assert ent.n_slots() / (n_groups * n_slabs) < 44
+    mat = tm.SplitMatrix([sm, tm.CategoricalMatrix(c1), tm.CategoricalMatrix(c2)])
+    seen = []
+    orig = _lib.call
+
+    def spy(name, *a):
+        seen.append(name)
+        return orig(name, *a)
+
+    xsplit_mod.call = spy
+    try:
+        full = mat.sandwich(d)
+    finally:
+        xsplit_mod.call = orig
+    assert any(s.startswith("tm_multi_cat_sparse_sandwich_ent") for s in seen), seen
+    coo = S.tocoo()
+    wv = d[coo.row] * coo.data
+    i_s = np.asarray(mat.indices[0])
+    for codes, lv, idx in ((c1, 12, mat.indices[1]), (c2, 5, mat.indices[2])):
+        want = sps.coo_matrix((wv, (codes[coo.row], coo.col)), shape=(lv, m)).toarray()
+        got = np.asarray(full)[np.ix_(np.asarray(idx), i_s)]
+        err = np.abs(got - want).max() / np.abs(want).max()
+        print(f"10M cat x sparse ({lv} levels): err {err:.3e}")
+        assert err < 1e-10
+        assert np.abs(np.asarray(full)[np.ix_(i_s, np.asarray(idx))] - want.T).max() / np.abs(want).max() < 1e-10
