@@ -225,6 +225,44 @@ int tm_dense_sandwich_diag_f32(const float *X, int64_t n, int64_t m, const float
 int tm_dense_sandwich_diag_f64(const double *X, int64_t n, int64_t m, const double *dm, const double *center,
                                double *out, void *stream);
 
+/* GLM ROW FUNCTIONS (csrc/glm.hip).  family selects mu(eta), the half unit deviance l, r = dl/deta and the
+ * Fisher weight h of one row (links: identity, log, logit, log):
+ *   TM_GLM_GAUSSIAN  mu = eta                 l = (y - mu)^2 / 2                             r = mu - y          h = 1
+ *   TM_GLM_POISSON   mu = exp(eta)            l = y (log y - eta) - (y - mu)                 r = mu - y          h = mu
+ *   TM_GLM_BINOMIAL  mu = 1 / (1 + exp(-eta)) l = softplus(eta) - y eta + y log y            r = mu - y          h = mu (1 - mu)
+ *                                                 + (1 - y) log(1 - y)
+ *   TM_GLM_GAMMA     mu = exp(eta)            l = y exp(-eta) - 1 - log y + eta              r = 1 - y exp(-eta) h = 1
+ * with 0 log 0 = 0, softplus(eta) = max(eta, 0) + log1p(exp(-|eta|)) and mu (1 - mu) from the same exp(-|eta|).
+ * The math runs in float64 for both data types; eta is not clamped (overflow gives inf) and the domains of y
+ * (y >= 0, 0 <= y <= 1, y > 0) are the caller's contract.  With weights wt (NULL = 1) the outputs are
+ * r[i] = wt[i] r_i, d[i] = wt[i] h_i and loss[0] = sum_i wt[i] l_i; a row with wt[i] == 0 gives exactly 0 in all
+ * three whatever its eta (the zero is selected, not multiplied: zero weights are a row mask). */
+enum { TM_GLM_GAUSSIAN = 0, TM_GLM_POISSON = 1, TM_GLM_BINOMIAL = 2, TM_GLM_GAMMA = 3 };
+
+/* K9: GLM loss, gradient slice and Hessian weights from ONE pass over a C-ordered (row-major) block:
+ *   eta[i] = (X[i,:] - center) . u + shift[0] + t_add[i]     (r, d, loss) = the family's row function of eta, y, wt
+ *   g = (X - 1 center')' r
+ * K8's row walk (tm_dense_sandwich_matvec_*: same lane layouts, width limits and meaning of center / shift /
+ * t_add, each of which may be NULL); the row sums of a wave step are evaluated ONCE, one row per lane, and r goes
+ * back to the row's lanes.  u, center, g: length m; y, wt, t_add, eta, r, d: length n; loss: ONE float64 on the
+ * device.  g, eta, r, d and loss are OVERWRITTEN.  Per-workgroup partials of g and of the loss are summed in a
+ * fixed order by a second launch (no atomics: bitwise reproducible).  TM_EINVAL for an unknown family or a
+ * block outside the width limits. */
+int tm_dense_glm_loss_grad_f32(const float *X, int64_t n, int64_t m, const float *u, int family, const float *y,
+                               const float *wt, const float *t_add, const float *center, const float *shift,
+                               float *g, float *eta, float *r, float *d, double *loss, void *stream);
+int tm_dense_glm_loss_grad_f64(const double *X, int64_t n, int64_t m, const double *u, int family, const double *y,
+                               const double *wt, const double *t_add, const double *center, const double *shift,
+                               double *g, double *eta, double *r, double *d, double *loss, void *stream);
+
+/* The same row function on an existing eta (length n) in one streaming launch: r, d (length n) and loss[0] are
+ * overwritten; the loss is summed in a fixed order (no atomics).  For matrices K9 does not take (no dense
+ * block, too wide, no row-major twin, row parts): matvec, this, transpose_matvec(r). */
+int tm_glm_rowfn_f32(int family, const float *eta, const float *y, const float *wt, int64_t n, float *r, float *d,
+                     double *loss, void *stream);
+int tm_glm_rowfn_f64(int family, const double *eta, const double *y, const double *wt, int64_t n, double *r,
+                     double *d, double *loss, void *stream);
+
 /* X' diag(d) X of an unrestricted, 16-byte aligned, C-ordered FLOAT32 block of m = 4 k <= 256 columns
  * on the bf16 matrix cores: every element of diag(sqrt|d|) X is split into three bf16 pieces (24
  * mantissa bits) and the six leading piece products are accumulated in f32 with

@@ -415,6 +415,37 @@ class DenseMatrix(MatrixBase):
             g = g[D.idx_dev(a.cols, torch.int64)]
         return a.finish(g)
 
+    def _glm_dev(self, family, u_full, y, wt, t_add, shift=None, centers=None):
+        """SplitMatrix._glm_dev for a lone dense block: (loss, g, eta, r, d, fix) from one pass
+        (tm_dense_glm_loss_grad_*), or None when the kernel does not take the block.  centers: {0: column centres}
+        or None."""
+        blk = self._smv_block()
+        if blk is None:
+            return None
+        c = None if centers is None else centers.get(0)
+        if c is not None:
+            c = c.to(u_full.dtype).contiguous()
+            cu = (c * u_full).sum().reshape(1)
+            shift = cu if shift is None else shift + cu
+        loss, g, eta, r, d = xd.dense_glm_loss_grad(
+            blk, u_full.contiguous(), family, y, wt, t_add=t_add, center=c,
+            shift=None if shift is None else shift.to(u_full.dtype).contiguous())
+        return loss, g, eta, r, d, (None if c is None else (None, c))
+
+    def glm_loss_grad(self, family, beta, y, weights=None, offset=None):
+        """(loss, grad, eta, d) of a GLM at beta (MatrixBase.glm_loss_grad).  ONE pass over the block
+        (tm_dense_glm_loss_grad_*: the sandwich_matvec row walk with the family's row function in place of d * t)
+        for the blocks sandwich_matvec takes in one pass; matvec, tm_glm_rowfn_* and transpose_matvec for an
+        F-ordered block without a twin and for wider blocks."""
+        from .matrix_base import _glm_args, _glm_compose
+
+        a = _glm_args(self, family, beta, y, weights, offset)
+        if self._smv_block() is None:
+            return a.finish(*_glm_compose(self, a))
+        b, yd, wt, off = a.dev()
+        loss, g, eta, _, d, _ = self._glm_dev(a.family, b, yd, wt, off)
+        return a.finish(loss, g, eta, d)
+
     def _sdiag_dev(self, d, rows, center=None):
         """out[j] = sum_{r in rows} d[r] (x_rj - center_j)^2 over ALL columns (device, the block dtype).  d: device
         vector over all rows; rows: int32 device tensor or None; center: device vector of the block dtype or

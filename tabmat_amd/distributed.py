@@ -6,7 +6,7 @@ row-partitioned and needs no exchange.  One process per GPU (torch.distributed, 
 p x p partial with the single-GPU kernels; the only collective on the data path is one
 all-reduce of the small result (8 MB at p = 1024) per sandwich, or of a length-p vector per
 transpose_matvec, or of both packed into one buffer per sandwich_and_transpose_matvec, or of the length-k result of
-sandwich_matvec.  No NCCL pattern of the reference is translated: the reference has none.
+sandwich_matvec, or of the gradient and the loss of glm_loss_grad packed into one buffer.  No NCCL pattern of the reference is translated: the reference has none.
 """
 from __future__ import annotations
 
@@ -75,7 +75,8 @@ class RowShardedMatrix:
                  local_sandwich_matvec: Optional[Callable] = None,
                  local_sandwich_diag: Optional[Callable] = None,
                  bounds: Optional[tuple] = None, n_global: Optional[int] = None,
-                 always_reduce: bool = False):
+                 always_reduce: bool = False,
+                 local_glm_loss_grad: Optional[Callable] = None):
         self.local = local
         self.always_reduce = always_reduce   # issue the collective at world size 1 too (tests)
         self.group = group
@@ -93,6 +94,8 @@ class RowShardedMatrix:
             self._both = lambda d, v, rows, cols: (self._sandwich(d, rows, cols), self._tmv(v, rows, cols))
         self._smv = local_sandwich_matvec or (lambda d, u, rows, cols: local.sandwich_matvec(d, u, rows, cols))
         self._sdiag = local_sandwich_diag or (lambda d, rows, cols: local.sandwich_diag(d, rows, cols))
+        self._glm = local_glm_loss_grad or (
+            lambda family, beta, y, weights, offset: local.glm_loss_grad(family, beta, y, weights, offset))
         self.shape = local.shape
         self.dtype = local.dtype
 
@@ -193,6 +196,29 @@ class RowShardedMatrix:
         """d: global length-n vector; rows: global row ids or None."""
         lo, hi = self.bounds
         return self.sandwich_diag(self.local_slice(d), bucket_rows(rows, lo, hi), cols)
+
+    def glm_loss_grad(self, family, beta, y, weights=None, offset=None):
+        """(loss, grad, eta, d) of the whole matrix's GLM at beta: beta replicated on every rank, y / weights /
+        offset the LOCAL slices.  The local gradient and loss are packed into one float64 buffer and summed with
+        ONE all-reduce; eta and d stay local (they are row-partitioned, like matvec).  loss comes back as the
+        local call returns it: a Python float for numpy inputs, a 0-dim float64 device tensor else."""
+        loss, g, eta, d = self._glm(family, beta, y, weights, offset)
+        if not dist.is_initialized() or (self.world_size == 1 and not self.always_reduce):
+            return loss, g, eta, d
+        if isinstance(g, torch.Tensor):
+            buf = self._all_reduce(torch.cat([g.reshape(-1).to(torch.float64),
+                                              torch.as_tensor(loss, dtype=torch.float64, device=g.device).reshape(1)]))
+            loss_out = buf[-1] if isinstance(loss, torch.Tensor) else float(buf[-1].item())
+            return loss_out, buf[:-1].to(g.dtype), eta, d
+        g = np.asarray(g)
+        buf = self._all_reduce(np.concatenate([g.astype(np.float64).ravel(), [float(loss)]]))
+        return float(buf[-1]), buf[:-1].astype(g.dtype, copy=False), eta, d
+
+    def glm_loss_grad_global(self, family, beta, y, weights=None, offset=None):
+        """y, weights, offset: global length-n vectors (or None); beta: replicated."""
+        sl = self.local_slice
+        return self.glm_loss_grad(family, beta, sl(y), None if weights is None else sl(weights),
+                                  None if offset is None else sl(offset))
 
     def matvec(self, v, cols=None, out=None):
         """Row-partitioned output: the local rows of X v; no collective."""

@@ -279,3 +279,46 @@ def dense_sandwich_diag(X: DenseDev, dm, center=None):
     call(f"tm_dense_sandwich_diag_{D.fsuf(X.buf)}", D.p(X.buf), X.n, X.m, D.p(dm), D.p(center), D.p(out),
          D.stream_ptr())
     return out
+
+
+# family names of glm_loss_grad -> the TM_GLM_* codes of include/tabmat_hip.h
+GLM_FAMILIES = {"gaussian": 0, "poisson": 1, "binomial": 2, "gamma": 3}
+
+
+def dense_glm_loss_grad(X: DenseDev, u, family: int, y, wt=None, t_add=None, center=None, shift=None):
+    """(loss, g, eta, r, d) from ONE pass over a C-ordered block (tm_dense_glm_loss_grad_*): eta = (X - 1 center') u +
+    shift + t_add, (r, d, loss) the family's weighted row function of (eta, y, wt), g = (X - 1 center')' r.  family:
+    a GLM_FAMILIES code; u, center: length X.m; y, wt, t_add: length X.n; shift: a one-element device tensor; all
+    of the block's dtype; wt / t_add / center / shift may be None.  loss: 0-dim float64 device tensor."""
+    import torch
+
+    g = D.out_buf((X.m,), X.dtype)
+    eta, r, d = (D.out_buf((X.n,), X.dtype) for _ in range(3))
+    loss = D.out_buf((), torch.float64)
+    D.same_float("dense_glm_loss_grad", X.buf, u, y, wt, t_add, center, shift)
+    assert sandwich_matvec_supported(X)
+    assert u.numel() == X.m and u.is_contiguous()
+    for v in (y, wt, t_add):
+        assert v is None or (v.numel() == X.n and v.is_contiguous())
+    assert center is None or (center.numel() == X.m and center.is_contiguous())
+    assert shift is None or shift.numel() == 1
+    call(f"tm_dense_glm_loss_grad_{D.fsuf(X.buf)}", D.p(X.buf), X.n, X.m, D.p(u), int(family), D.p(y), D.p(wt),
+         D.p(t_add), D.p(center), D.p(shift), D.p(g), D.p(eta), D.p(r), D.p(d), D.p(loss), D.stream_ptr())
+    return loss, g, eta, r, d
+
+
+def glm_rowfn(family: int, eta, y, wt=None):
+    """(loss, r, d): the family's weighted row function of an existing eta in one streaming launch
+    (tm_glm_rowfn_*; the device function K9 evaluates).  eta, y, wt (or None): 1-D device tensors of one float
+    dtype and length; loss: 0-dim float64 device tensor."""
+    import torch
+
+    D.same_float("glm_rowfn", eta, y, wt)
+    n = eta.numel()
+    assert eta.is_contiguous() and y.numel() == n and y.is_contiguous()
+    assert wt is None or (wt.numel() == n and wt.is_contiguous())
+    r, d = D.out_buf((n,), eta.dtype), D.out_buf((n,), eta.dtype)
+    loss = D.out_buf((), torch.float64)
+    call(f"tm_glm_rowfn_{D.fsuf(eta)}", int(family), D.p(eta), D.p(y), D.p(wt), n, D.p(r), D.p(d), D.p(loss),
+         D.stream_ptr())
+    return loss, r, d

@@ -62,6 +62,21 @@ class MatrixBase(ABC):
             return a.finish(a.trivial)
         return _sd_compose(self, a)
 
+    def glm_loss_grad(self, family, beta, y, weights=None, offset=None):
+        """(loss, grad, eta, d) of a GLM at beta -- what a solver needs at every iterate and line-search trial.
+        family: "gaussian", "poisson", "binomial" or "gamma" (links: identity, log, logit, log).  With
+        eta = self @ beta + offset, w = weights (1 when None) and the family's half unit deviance l, r = dl/deta
+        and Fisher weight h per row (include/tabmat_hip.h): loss = sum w l (half the deviance, summed in float64),
+        grad = self' (w r) (its gradient in beta), d = w h (ready for sandwich / sandwich_matvec /
+        sandwich_diag).  A row with weight 0 contributes exactly 0 to loss and grad and has d = 0 whatever its eta
+        (zero weights are a row mask); eta is not clamped; the domains of y are the caller's contract.  beta: 1-D of
+        length p; y, weights, offset: 1-D of length n.  Results are on beta's side: numpy grad / eta / d and a
+        Python float loss for a numpy beta, device tensors (loss 0-dim float64, no sync) for a device beta; grad,
+        eta and d have the matrix dtype.  This default is matvec, one row-function launch (tm_glm_rowfn_*) and
+        transpose_matvec; classes with a one-pass dense kernel override it."""
+        a = _glm_args(self, family, beta, y, weights, offset)
+        return a.finish(*_glm_compose(self, a))
+
     @abstractmethod
     def getcol(self, i: int):
         ...
@@ -284,3 +299,70 @@ def _sd_compose(mat, a):
         x = np.asarray(mat.getcol(int(j)).toarray(), dtype=d.dtype).reshape(-1)
         out[q] = np.asarray(mat.transpose_matvec(d * x, rows=a.rows, cols=[int(j)])).reshape(-1)[0]
     return D.to_dev(out, D.torch_dtype(a.out_dtype)) if a.on_dev else out
+
+
+class _GlmArgs:
+    """The checked arguments of one glm_loss_grad call (_glm_args)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def dev(self):
+        """(beta, y, weights or None, offset or None) as contiguous device vectors of the matrix dtype."""
+        from . import _device as D
+
+        tdt = D.torch_dtype(self.dtype)
+        return tuple(None if v is None else D.to_dev(v, tdt) for v in (self.beta, self.y, self.weights, self.offset))
+
+    def finish(self, loss, g, eta, d):
+        """(loss, grad, eta, d) on beta's side."""
+        from . import _device as D
+
+        if self.on_dev:
+            return loss.reshape(()), g, eta, d
+        return float(loss.item()), D.to_host(g), D.to_host(eta), D.to_host(d)
+
+
+def _glm_args(mat, family, beta, y, weights, offset):
+    """Host-side checks of glm_loss_grad (no device work): a known family, beta 1-D of length p, y / weights /
+    offset 1-D of length n."""
+    from . import _device as D
+    from .ext.dense import GLM_FAMILIES
+
+    if not isinstance(family, str) or family not in GLM_FAMILIES:
+        raise ValueError(f"unknown family {family!r}; glm_loss_grad knows {sorted(GLM_FAMILIES)}")
+    n, p = mat.shape
+    on_dev = D.is_dev(beta)
+    if not on_dev:
+        beta = np.asarray(beta)
+    if beta.ndim > 1:
+        raise NotImplementedError("glm_loss_grad is only implemented for 1d arrays.")
+    if beta.ndim != 1 or beta.shape[0] != p:
+        raise ValueError(f"beta has shape {tuple(beta.shape)}; glm_loss_grad needs length {p} (the columns)")
+    vecs = {}
+    for name, v in (("y", y), ("weights", weights), ("offset", offset)):
+        if v is None:
+            if name == "y":
+                raise ValueError("glm_loss_grad needs y")
+        else:
+            if not D.is_dev(v):
+                v = np.asarray(v)
+            if v.ndim != 1 or v.shape[0] != n:
+                raise ValueError(f"{name} has shape {tuple(v.shape)}; glm_loss_grad needs length {n} (the rows)")
+        vecs[name] = v
+    return _GlmArgs(mat=mat, family=GLM_FAMILIES[family], beta=beta, n=n, p=p, on_dev=on_dev,
+                    dtype=np.dtype(mat.dtype), **vecs)
+
+
+def _glm_compose(mat, a):
+    """(loss, g, eta, d) as device tensors from matvec, tm_glm_rowfn_* and transpose_matvec: the two-pass form of
+    glm_loss_grad, for any object with the two products."""
+    from .ext.dense import glm_rowfn
+
+    beta, y, wt, off = a.dev()
+    eta = mat.matvec(beta)
+    if off is not None:
+        eta = eta + off
+    eta = eta.contiguous()
+    loss, r, d = glm_rowfn(a.family, eta, y, wt)
+    return loss, mat.transpose_matvec(r), eta, d

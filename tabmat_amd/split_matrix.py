@@ -18,6 +18,7 @@ from . import _device as D
 from .categorical_matrix import CategoricalMatrix
 from .dense_matrix import DenseMatrix
 from .ext import split as xsplit
+from .ext.dense import dense_glm_loss_grad as xd_glm
 from .ext.dense import dense_sandwich_matvec as xd_smv
 from .matrix_base import MatrixBase
 from .sparse_matrix import SparseMatrix
@@ -1215,6 +1216,47 @@ class SplitMatrix(MatrixBase):
                         shift=None if shift is None else shift.to(u_full.dtype).contiguous(), want_w=True)
         g, _ = self._transpose_matvec_dev(w, None, None, done={bi: g_D})
         return g, w, (None if c is None else (idx, c))
+
+    def _glm_dev(self, family, u_full, y, wt, t_add, shift=None, centers=None):
+        """(loss, g, eta, r, d, fix) of glm_loss_grad over ALL columns (device, the matrix dtype), or None when no
+        dense block takes the fused pass (or the matrix runs in row parts).  As _smv_dev: the other blocks'
+        X_b u_b comes first and t_add (the offset) is added to it; one pass over the fused dense block D
+        (tm_dense_glm_loss_grad_*) then gives eta = X_D u_D + that + shift, the family's r, d and loss, and
+        g_D = X_D' r; the other blocks' transpose_matvec runs on r.  centers / shift / fix as in _smv_dev."""
+        bi = self._smv_dense_block()
+        if bi is None or self._parts() is not None:
+            return None
+        mat = self.matrices[bi]
+        blk = mat._smv_block()
+        idx = self._full_dev_indices()[bi]
+        u_D = u_full[idx].contiguous()
+        t_o = self._matvec1_dev(u_full, None, skip=(bi,))
+        if t_add is not None:
+            t_o += t_add
+        c = None if centers is None else centers.get(bi)
+        if c is not None:
+            c = c.to(u_full.dtype).contiguous()
+            cu = (c * u_D).sum().reshape(1)
+            shift = cu if shift is None else shift + cu
+        loss, g_D, eta, r, d = xd_glm(blk, u_D, family, y, wt, t_add=t_o, center=c,
+                                      shift=None if shift is None else shift.to(u_full.dtype).contiguous())
+        g, _ = self._transpose_matvec_dev(r, None, None, done={bi: g_D})
+        return loss, g, eta, r, d, (None if c is None else (idx, c))
+
+    def glm_loss_grad(self, family, beta, y, weights=None, offset=None):
+        """(loss, grad, eta, d) of a GLM at beta (MatrixBase.glm_loss_grad).  The widest dense block the one-pass
+        kernel takes is read ONCE (_glm_dev): the other blocks' matvec, the dense pass with the family's row
+        function, the other blocks' transpose_matvec on r.  Matrices without such a block, and row parts, run
+        matvec, tm_glm_rowfn_* and transpose_matvec."""
+        from .matrix_base import _glm_args, _glm_compose
+
+        a = _glm_args(self, family, beta, y, weights, offset)
+        b, yd, wt, off = a.dev()
+        res = self._glm_dev(a.family, b, yd, wt, off)
+        if res is None:
+            return a.finish(*_glm_compose(self, a))
+        loss, g, eta, _, d, _ = res
+        return a.finish(loss, g, eta, d)
 
     def _transpose_matvec_dev(self, v, rows_n, cols_n, done=None):
         """The product of transpose_matvec as a device tensor of the matrix dtype, and the column selection it

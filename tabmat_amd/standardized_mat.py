@@ -280,6 +280,42 @@ class StandardizedMatrix:
             g = g[D.idx_dev(a.cols, torch.int64)]
         return a.finish(g)
 
+    def glm_loss_grad(self, family, beta, y, weights=None, offset=None):
+        """(loss, grad, eta, d) of a GLM at beta on the standardized matrix (MatrixBase.glm_loss_grad): with
+        X_s = X diag(mult) + 1 shift', eta = X (mult beta) + shift . beta + offset and
+        grad = mult (X' r) + shift sum(r).  The inner matrix's one-pass path (DenseMatrix / SplitMatrix._glm_dev)
+        runs with the column centres of its fused dense block (float64, as in sandwich_matvec): that block is read
+        as X - 1 c', so eta does not cancel mean-sized terms.  matvec, tm_glm_rowfn_* and transpose_matvec
+        otherwise."""
+        from .matrix_base import _glm_args, _glm_compose
+
+        a = _glm_args(self, family, beta, y, weights, offset)
+        tdt = D.torch_dtype(self.dtype)
+        mat = self.mat
+        res = None
+        if hasattr(mat, "_glm_dev"):
+            b, yd, wt, off = a.dev()
+            au = b if self.mult is None else b * self._mult_dev(None, tdt)
+            s0 = (self._shift_dev(None, tdt) * b).sum().reshape(1)
+            cen = self._centering() if tdt == torch.float64 else None
+            res = mat._glm_dev(a.family, au.contiguous(), yd, wt, off, shift=s0,
+                               centers=None if cen is None else cen[2])
+        if res is None:
+            return a.finish(*_glm_compose(self, a))
+        loss, g, eta, r, d, fix = res
+        sr = r.sum(dtype=torch.float64).to(tdt)
+        if fix is not None:
+            pos, c = fix
+            if pos is None:
+                g = g + c * sr
+            else:
+                g = g.clone()
+                g[pos] += c * sr
+        if self.mult is not None:
+            g = g * self._mult_dev(None, tdt)
+        g = g + self._shift_dev(None, tdt) * sr
+        return a.finish(loss, g, eta, d)
+
     def _diag_centering(self):
         """(delta, dense mask, {block: centres}) for sandwich_diag, cached.  A dense column j is read as
         x_j - c_j with c_j = -shift_j / mult_j inside the kernel (both data types), so self[:, j] =
