@@ -3,7 +3,7 @@ it) against the composition a caller had to spell out before -- matvec, the torc
 examples/glm_newton_cg.py (its Poisson lines, and the same spelling for the other families), transpose_matvec --
 and against sandwich_matvec on the same design: the row walk without transcendentals, the floor of the fused call.
 Device vectors, a synchronize around every call, interleaved A / B / C in one process, min / median of 16 calls after
-3 warm-up calls each.  Also the register / scratch / occupancy report of every K9 instantiation next to K8's (from
+3 warm-up calls each.  Also the register / scratch / occupancy report of every K9 instantiation next to K8's and K8d's (from
 hipcc's -Rpass-analysis=kernel-resource-usage; needs no GPU).
 
     python scripts/dev/time_glm_loss_grad.py [rows] [--out profiles/glm_loss_grad.txt] [--no-timings] [--no-resources]
@@ -139,8 +139,8 @@ def timings(n):
 
 
 def resources():
-    """vgpr / sgpr / scratch / waves per SIMD of every dense_glm_loss_grad_kernel and dense_sandwich_matvec_kernel
-    instantiation, from the compiler's resource report."""
+    """vgpr / sgpr / scratch / waves per SIMD of every dense_glm_loss_grad_kernel, dense_sandwich_matvec_kernel and
+    dense_sandwich_diag_kernel instantiation, from the compiler's resource report."""
     csrc = os.path.join(ROOT, "tabmat_amd", "csrc")
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     table = {}
@@ -160,15 +160,15 @@ def resources():
                     cur[m.group(1)] = int(m.group(3))
     rows = {}
     for name, v in table.items():
-        m = re.search(r"\d+(dense_glm_loss_grad_kernel|dense_sandwich_matvec_kernel)I([fd])Li(\d+)ELi(\d+)ELi(\d+)ELi(\d+)", name)
+        m = re.search(r"\d+dense_(glm_loss_grad|sandwich_matvec|sandwich_diag)_kernelI([fd])Li(\d+)ELi(\d+)ELi(\d+)ELi(\d+)", name)
         if m:
             key = ("f32" if m.group(2) == "f" else "f64", int(m.group(3)), int(m.group(4)), int(m.group(5)), int(m.group(6)))
-            rows.setdefault(key, {})["K9" if "glm" in m.group(1) else "K8"] = v
+            rows.setdefault(key, {})[{"glm_loss_grad": "K9", "sandwich_matvec": "K8", "sandwich_diag": "K8d"}[m.group(1)]] = v
         m = re.search(r"\d+glm_rowfn_kernelI([fd])Li(\d+)", name)
         if m:
             rows[("f32" if m.group(1) == "f" else "f64", int(m.group(2)), 0, 0, 0)] = {"rowfn": v}
     say("== registers, scratch and waves per SIMD (hipcc -Rpass-analysis=kernel-resource-usage, gfx950) ==")
-    say("  layout                           K9: vgpr scratch waves      K8: vgpr scratch waves")
+    say("  layout                           K9: vgpr scratch waves      K8: vgpr scratch waves     K8d: vgpr scratch waves")
     for key in sorted(rows):
         dt, vec, lpr, nl, r = key
         v = rows[key]
@@ -176,9 +176,8 @@ def resources():
             k = v["rowfn"]
             say(f"  glm_rowfn {dt} VEC={vec}:              {k['VGPRs']:8d} {k['ScratchSize']:7d} {k['Occupancy']:5d}")
             continue
-        a, b = v["K9"], v["K8"]
-        say(f"  {dt} VEC={vec} LPR={lpr:2d} NL={nl} R={r}        {a['VGPRs']:8d} {a['ScratchSize']:7d} {a['Occupancy']:5d}"
-            f"        {b['VGPRs']:8d} {b['ScratchSize']:7d} {b['Occupancy']:5d}")
+        say(f"  {dt} VEC={vec} LPR={lpr:2d} NL={nl} R={r}" + "".join(
+            f"        {k['VGPRs']:8d} {k['ScratchSize']:7d} {k['Occupancy']:5d}" for k in (v["K9"], v["K8"], v["K8d"])))
 
 
 def main():

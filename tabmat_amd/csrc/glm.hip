@@ -5,9 +5,9 @@
 //   (l_r, r_r, h_r) = the family's row function of (eta_r, y_r)          (glm_row below, float64)
 //   r[r] = wt_r r_r     d[r] = wt_r h_r     loss = sum_r wt_r l_r     g = sum_r (x_r - c) wt_r r_r
 //
-// The row walk is K8's (sandwich_matvec.hip): a wave loads R rows per lane segment into registers, reduces the
-// dot products across the lanes of each row, and adds x_r r_r into per-lane column accumulators while the rows
-// are still in registers.  Between the two the row function runs ONCE per wave step: after the reduction every
+// The row walk is the shared one (dense_rowwalk.hpp): a wave loads R rows per lane segment into registers, reduces
+// the dot products across the lanes of each row, and adds x_r r_r into per-lane column accumulators while the
+// rows are still in registers.  Between the two the row function runs ONCE per wave step: after the reduction every
 // lane of a segment holds the R row sums of that segment, so lane k of the segment (k < R <= 8 <= LPR) takes row
 // k -- a register select, nothing crosses lanes -- and a step's R * (64 / LPR) rows are evaluated side by side in
 // as many lanes.  r then goes back to the row's lanes (v_readlane when a row spans the wave, ds_bpermute
@@ -15,19 +15,15 @@
 //
 // Sums are fixed-order: per-workgroup partials of g plus one loss slot, finished by a second launch.  No
 // floating-point atomics; results are bitwise reproducible.
-#include <algorithm>
-
-#include "common.hpp"
+#include "dense_rowwalk.hpp"
 #include "glm_math.hpp"
 
 namespace tmh {
 
+using namespace rowwalk;
+
 namespace {
 
-constexpr int GLM_THREADS = 256;
-constexpr int GLM_WAVES = GLM_THREADS / WAVE;
-constexpr int GLM_MAX_NL = 8;          // 16-byte loads per lane and row: m <= 64 * VEC * 8 (as K8)
-constexpr int GLM_MAX_WG = 1024;
 constexpr int GLM_ROWFN_MAX_WG = 1024;      // all resident at once (4 per CU): no tail of late workgroups
 
 // one row of a GLM: half unit deviance l, r = dl/deta, Fisher weight h (include/tabmat_hip.h).  `family` is
@@ -83,18 +79,6 @@ __device__ __forceinline__ void glm_row_weighted(int family, double eta, double 
     }
 }
 
-// sum over the LPR lanes of each row segment; every lane of the segment gets the sum (as K8)
-template <int LPR>
-__device__ __forceinline__ double segment_allreduce(double v) {
-    v += dpp_xor<1>(v);
-    v += dpp_xor<2>(v);
-    v += dpp_xor<4>(v);
-    if constexpr (LPR >= 16) v += dpp_xor<8>(v);
-    if constexpr (LPR >= 32) v += __shfl_xor(v, 16, 64);
-    if constexpr (LPR >= 64) v += __shfl_xor(v, 32, 64);
-    return v;
-}
-
 // the value lane K of the own row segment holds, in every lane of the segment
 template <int LPR, int K>
 __device__ __forceinline__ double segment_bcast(double v, int seg) {
@@ -113,7 +97,7 @@ __device__ __forceinline__ double block_sum_fixed(double v, double *slot) {
     for (int s = 1; s < WAVE; s <<= 1) v += __shfl_xor(v, s, 64);
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = threadIdx.x / WAVE;
-    for (int wv = 0; wv < GLM_WAVES; ++wv) {
+    for (int wv = 0; wv < WAVES; ++wv) {
         if (wave == wv && lane == 0) *slot = wv == 0 ? v : *slot + v;
         __syncthreads();
     }
@@ -123,7 +107,7 @@ __device__ __forceinline__ double block_sum_fixed(double v, double *slot) {
 // VEC: elements per load (16 / sizeof(F) on 16-byte aligned rows, 1 else); LPR: lanes per row (8 .. 64, a power
 // of two); NL: loads per lane and row (> 1 only with LPR = 64); R: rows per lane segment and step (<= 8).
 template <typename F, int VEC, int LPR, int NL, int R>
-__global__ __launch_bounds__(GLM_THREADS) void dense_glm_loss_grad_kernel(
+__global__ __launch_bounds__(THREADS) void dense_glm_loss_grad_kernel(
     const F *__restrict__ X, int64_t n, int m, const F *__restrict__ u, int family, const F *__restrict__ y,
     const F *__restrict__ wt, const F *__restrict__ t_add, const F *__restrict__ center,
     const F *__restrict__ shift, int64_t rows_per_wg, double *__restrict__ part, F *__restrict__ eta,
@@ -138,27 +122,17 @@ __global__ __launch_bounds__(GLM_THREADS) void dense_glm_loss_grad_kernel(
     const int seg = lane / LPR;
     const int sl = lane % LPR;
 
-    // this lane's columns: (q * LPR + sl) * VEC + e
     F uu[NL][VEC], cc[NL][VEC];
     double acc[NL][VEC];
     bool live[NL];
-#pragma unroll
-    for (int q = 0; q < NL; ++q) {
-        const int j0 = (q * LPR + sl) * VEC;
-        live[q] = j0 < m;                              // m % VEC == 0: a vector is all in or all out
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            uu[q][e] = live[q] ? u[j0 + e] : F(0);
-            cc[q][e] = (live[q] && center) ? center[j0 + e] : F(0);
-            acc[q][e] = 0.0;
-        }
-    }
+    lane_columns<LPR>(m, sl, center, live, cc, acc);
+    lane_u<LPR>(m, sl, u, uu);
     const double s0 = shift ? (double)shift[0] : 0.0;
     double lacc = 0.0;                                 // this lane's share of the loss
 
     const int64_t r_begin = (int64_t)blockIdx.x * rows_per_wg;
     const int64_t r_end = min(r_begin + rows_per_wg, n);
-    for (int64_t r0 = r_begin + (int64_t)wave * ROWS; r0 < r_end; r0 += (int64_t)GLM_WAVES * ROWS) {
+    for (int64_t r0 = r_begin + (int64_t)wave * ROWS; r0 < r_end; r0 += (int64_t)WAVES * ROWS) {
         vec_t x[R][NL];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -211,31 +185,9 @@ __global__ __launch_bounds__(GLM_THREADS) void dense_glm_loss_grad_kernel(
         });
     }
 
-    // the row segments of a wave hold the same columns: fold them (fixed xor tree)
-#pragma unroll
-    for (int s = LPR; s < WAVE; s <<= 1)
-#pragma unroll
-        for (int q = 0; q < NL; ++q)
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) acc[q][e] += __shfl_xor(acc[q][e], s, 64);
-    // then the waves, one after the other
-    for (int wv = 0; wv < GLM_WAVES; ++wv) {
-        if (wave == wv && seg == 0) {
-#pragma unroll
-            for (int q = 0; q < NL; ++q)
-                if (live[q]) {
-#pragma unroll
-                    for (int e = 0; e < VEC; ++e) {
-                        const int j = (q * LPR + sl) * VEC + e;
-                        glm_red[j] = wv == 0 ? acc[q][e] : glm_red[j] + acc[q][e];
-                    }
-                }
-        }
-        __syncthreads();
-    }
+    fold_columns<LPR>(acc, live, glm_red);
     block_sum_fixed(lacc, &glm_red[m]);
-    double *dst = part + (int64_t)blockIdx.x * (m + 1);
-    for (int j = threadIdx.x; j <= m; j += GLM_THREADS) dst[j] = glm_red[j];
+    store_partial(glm_red, part, m + 1);
 }
 
 // the row function over an existing eta: grid-stride over vectors of VEC elements, GLM_ROWFN_U independent
@@ -244,21 +196,21 @@ __global__ __launch_bounds__(GLM_THREADS) void dense_glm_loss_grad_kernel(
 constexpr int GLM_ROWFN_U = 4;
 
 template <typename F, int VEC>
-__global__ __launch_bounds__(GLM_THREADS) void glm_rowfn_kernel(int family, const F *__restrict__ eta,
-                                                                 const F *__restrict__ y, const F *__restrict__ wt,
-                                                                 int64_t n, F *__restrict__ rout,
-                                                                 F *__restrict__ dout, double *__restrict__ part) {
+__global__ __launch_bounds__(THREADS) void glm_rowfn_kernel(int family, const F *__restrict__ eta,
+                                                             const F *__restrict__ y, const F *__restrict__ wt,
+                                                             int64_t n, F *__restrict__ rout,
+                                                             F *__restrict__ dout, double *__restrict__ part) {
     typedef F vec_t __attribute__((ext_vector_type(VEC)));
     constexpr int U = GLM_ROWFN_U;
     __shared__ double slot;
     const int64_t nfull = n / VEC;                     // whole vectors
     double lacc = 0.0;
-    for (int64_t v0 = (int64_t)blockIdx.x * (GLM_THREADS * U) + threadIdx.x; v0 < nfull;
-         v0 += (int64_t)gridDim.x * (GLM_THREADS * U)) {
+    for (int64_t v0 = (int64_t)blockIdx.x * (THREADS * U) + threadIdx.x; v0 < nfull;
+         v0 += (int64_t)gridDim.x * (THREADS * U)) {
         vec_t ev[U], yv[U], wv[U];
 #pragma unroll
         for (int k = 0; k < U; ++k) {
-            const int64_t v = v0 + (int64_t)k * GLM_THREADS;
+            const int64_t v = v0 + (int64_t)k * THREADS;
             if (v < nfull) {
                 ev[k] = *reinterpret_cast<const vec_t *>(eta + v * VEC);
                 yv[k] = *reinterpret_cast<const vec_t *>(y + v * VEC);
@@ -267,7 +219,7 @@ __global__ __launch_bounds__(GLM_THREADS) void glm_rowfn_kernel(int family, cons
         }
 #pragma unroll
         for (int k = 0; k < U; ++k) {
-            const int64_t v = v0 + (int64_t)k * GLM_THREADS;
+            const int64_t v = v0 + (int64_t)k * THREADS;
             if (v < nfull) {
                 vec_t rv, dv;
 #pragma unroll
@@ -298,78 +250,6 @@ __global__ __launch_bounds__(GLM_THREADS) void glm_rowfn_kernel(int family, cons
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-// g[j] = sum over the nb partials (rows of m + 1 doubles) in a fixed order, column m -> loss[0] (16 waves per 64
-// columns, fixed tree at the end)
-template <typename F>
-__global__ __launch_bounds__(1024) void glm_reduce_kernel(const double *__restrict__ part, int nb, int m,
-                                                          F *__restrict__ g, double *__restrict__ loss) {
-    __shared__ double red[16][64];
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int j = blockIdx.x * 64 + lane;
-    double s = 0.0;
-    if (j <= m)
-        for (int b = wave; b < nb; b += 16) s += part[(int64_t)b * (m + 1) + j];
-    red[wave][lane] = s;
-    __syncthreads();
-    if (wave == 0 && j <= m) {
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < 16; k += 4) t += (red[k][lane] + red[k + 1][lane]) + (red[k + 2][lane] + red[k + 3][lane]);
-        if (j < m) g[j] = (F)t;
-        else loss[0] = t;
-    }
-}
-
-template <typename F>
-struct GlmArgs {
-    const F *X;
-    int64_t n;
-    int m;
-    const F *u;
-    int family;
-    const F *y, *wt, *t_add, *center, *shift;
-    F *g, *eta, *r, *d;
-    double *loss;
-};
-
-template <typename F, int VEC, int LPR, int NL>
-int launch_glm(const GlmArgs<F> &a, hipStream_t st) {
-    constexpr int R = NL >= 8 ? 1 : 8 / NL;
-    constexpr int ROWS = R * (WAVE / LPR);
-    // contiguous runs of whole wave steps, at most GLM_MAX_WG of them (as K8)
-    const int64_t steps = ceil_div(a.n, ROWS);
-    const int64_t steps_per_wg = std::max<int64_t>(GLM_WAVES, ceil_div(steps, GLM_MAX_WG));
-    const int64_t rows_per_wg = steps_per_wg * ROWS;
-    const int nwg = (int)ceil_div(a.n, rows_per_wg);
-    void *ws = nullptr;
-    int rc = get_workspace((size_t)nwg * (a.m + 1) * sizeof(double), &ws, st);
-    if (rc) return rc;
-    double *part = static_cast<double *>(ws);
-    prof_begin(st);
-    hipLaunchKernelGGL((dense_glm_loss_grad_kernel<F, VEC, LPR, NL, R>), dim3(nwg), dim3(GLM_THREADS),
-                       (size_t)(a.m + 1) * sizeof(double), st, a.X, a.n, a.m, a.u, a.family, a.y, a.wt, a.t_add,
-                       a.center, a.shift, rows_per_wg, part, a.eta, a.r, a.d);
-    prof_end(st);
-    TM_LAUNCH_CHECK();
-    hipLaunchKernelGGL((glm_reduce_kernel<F>), dim3((unsigned)ceil_div(a.m + 1, 64)), dim3(1024), 0, st, part, nwg,
-                       a.m, a.g, a.loss);
-    TM_LAUNCH_CHECK();
-    return TM_OK;
-}
-
-template <typename F, int VEC>
-int dispatch_glm(const GlmArgs<F> &a, hipStream_t st) {
-    const int nvec = (a.m + VEC - 1) / VEC;            // vectors per row
-    if (nvec <= 8) return launch_glm<F, VEC, 8, 1>(a, st);
-    if (nvec <= 16) return launch_glm<F, VEC, 16, 1>(a, st);
-    if (nvec <= 32) return launch_glm<F, VEC, 32, 1>(a, st);
-    if (nvec <= 64) return launch_glm<F, VEC, 64, 1>(a, st);
-    if (nvec <= 128) return launch_glm<F, VEC, 64, 2>(a, st);
-    if (nvec <= 256) return launch_glm<F, VEC, 64, 4>(a, st);
-    return launch_glm<F, VEC, 64, 8>(a, st);
-}
-
 inline bool glm_family_ok(int family) { return family >= TM_GLM_GAUSSIAN && family <= TM_GLM_GAMMA; }
 
 }  // namespace
@@ -378,11 +258,10 @@ template <typename F>
 int run_dense_glm_loss_grad(const F *X, int64_t n, int64_t m, const F *u, int family, const F *y, const F *wt,
                             const F *t_add, const F *center, const F *shift, F *g, F *eta, F *r, F *d,
                             double *loss, hipStream_t st) {
-    constexpr int V = 16 / (int)sizeof(F);
     TM_REQUIRE(n >= 0 && m >= 0, "negative shape");
     TM_REQUIRE(glm_family_ok(family), "unknown family");
     TM_REQUIRE(m > 0, "a block without columns has no row walk: use tm_glm_rowfn");
-    TM_REQUIRE(m <= (int64_t)WAVE * V * GLM_MAX_NL, "more columns than tm_dense_glm_loss_grad serves");
+    TM_REQUIRE(m <= max_columns(FULL_VEC<F>), "more columns than tm_dense_glm_loss_grad serves");
     TM_REQUIRE(g && loss, "g and loss are required");
     TM_REQUIRE(n == 0 || (X && u && y && eta && r && d), "X, u, y, eta, r and d are required");
     if (n == 0) {
@@ -390,14 +269,16 @@ int run_dense_glm_loss_grad(const F *X, int64_t n, int64_t m, const F *u, int fa
         TM_HIP(hipMemsetAsync(loss, 0, sizeof(double), st));
         return TM_OK;
     }
-    const GlmArgs<F> a{X, n, (int)m, u, family, y, wt, t_add, center, shift, g, eta, r, d, loss};
-    const bool vec_ok = m % V == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-    // one element per load: only widths up to 512 (64 lanes x 8 loads)
-    if (!vec_ok) {
-        TM_REQUIRE(m <= (int64_t)WAVE * GLM_MAX_NL, "unaligned rows: at most 512 columns");
-        return dispatch_glm<F, 1>(a, st);
-    }
-    return dispatch_glm<F, V>(a, st);
+    const int vec = load_form(X, m);
+    TM_REQUIRE(vec != 0, "unaligned rows: at most 512 columns");
+    return dispatch<F>(vec, (int)m, [&](auto v, auto lpr, auto nl) {
+        constexpr int VEC = decltype(v)::value, LPR = decltype(lpr)::value, NL = decltype(nl)::value;
+        constexpr int R = rows_per_segment(NL);
+        return launch<F>(n, (int)m, 1, R * (WAVE / LPR), g, loss, st, [&](Geometry ge, size_t lds, double *part) {
+            hipLaunchKernelGGL((dense_glm_loss_grad_kernel<F, VEC, LPR, NL, R>), dim3(ge.nwg), dim3(THREADS), lds, st,
+                               X, n, (int)m, u, family, y, wt, t_add, center, shift, ge.rows_per_wg, part, eta, r, d);
+        });
+    });
 }
 
 template <typename F>
@@ -417,21 +298,21 @@ int run_glm_rowfn(int family, const F *eta, const F *y, const F *wt, int64_t n, 
                            reinterpret_cast<uintptr_t>(d);
     const bool vec_ok = (bits & 15) == 0;
     const int64_t nv = vec_ok ? ceil_div(n, V) : n;
-    const int nwg = (int)std::min<int64_t>(GLM_ROWFN_MAX_WG, ceil_div(nv, GLM_THREADS * GLM_ROWFN_U));
+    const int nwg = (int)std::min<int64_t>(GLM_ROWFN_MAX_WG, ceil_div(nv, THREADS * GLM_ROWFN_U));
     void *ws = nullptr;
     int rc = get_workspace((size_t)nwg * sizeof(double), &ws, st);
     if (rc) return rc;
     double *part = static_cast<double *>(ws);
     prof_begin(st);
     if (vec_ok)
-        hipLaunchKernelGGL((glm_rowfn_kernel<F, V>), dim3(nwg), dim3(GLM_THREADS), 0, st, family, eta, y, wt, n, r, d,
+        hipLaunchKernelGGL((glm_rowfn_kernel<F, V>), dim3(nwg), dim3(THREADS), 0, st, family, eta, y, wt, n, r, d,
                            part);
     else
-        hipLaunchKernelGGL((glm_rowfn_kernel<F, 1>), dim3(nwg), dim3(GLM_THREADS), 0, st, family, eta, y, wt, n, r, d,
+        hipLaunchKernelGGL((glm_rowfn_kernel<F, 1>), dim3(nwg), dim3(THREADS), 0, st, family, eta, y, wt, n, r, d,
                            part);
     prof_end(st);
     TM_LAUNCH_CHECK();
-    hipLaunchKernelGGL((glm_reduce_kernel<F>), dim3(1), dim3(1024), 0, st, part, nwg, 0, (F *)nullptr, loss);
+    hipLaunchKernelGGL((reduce_kernel<F>), dim3(1), dim3(1024), 0, st, part, nwg, 0, 1, (F *)nullptr, loss);
     TM_LAUNCH_CHECK();
     return TM_OK;
 }

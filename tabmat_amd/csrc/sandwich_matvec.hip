@@ -12,35 +12,18 @@
 // a row is narrower than 64 lanes) are summed in a fixed order and written as the workgroup's partial
 // g, which a second launch sums in a fixed order: no floating-point atomics, bitwise reproducible.
 // The products are formed in float64 for both data types (float32 data is widened on load).
-#include <algorithm>
-
-#include "common.hpp"
+#include "dense_rowwalk.hpp"
 
 namespace tmh {
 
+using namespace rowwalk;
+
 namespace {
-
-constexpr int SMV_THREADS = 256;
-constexpr int SMV_WAVES = SMV_THREADS / WAVE;
-constexpr int SMV_MAX_NL = 8;          // 16-byte loads per lane and row: m <= 64 * VEC * 8
-constexpr int SMV_MAX_WG = 1024;
-
-// sum over the LPR lanes of each row segment; every lane of the segment gets the sum
-template <int LPR>
-__device__ __forceinline__ double segment_allreduce(double v) {
-    v += dpp_xor<1>(v);
-    v += dpp_xor<2>(v);
-    v += dpp_xor<4>(v);
-    if constexpr (LPR >= 16) v += dpp_xor<8>(v);
-    if constexpr (LPR >= 32) v += __shfl_xor(v, 16, 64);
-    if constexpr (LPR >= 64) v += __shfl_xor(v, 32, 64);
-    return v;
-}
 
 // VEC: elements per load (16 / sizeof(F) on 16-byte aligned rows, 1 else); LPR: lanes per row (8 .. 64,
 // a power of two); NL: loads per lane and row (> 1 only with LPR = 64); R: rows per lane segment and step.
 template <typename F, int VEC, int LPR, int NL, int R>
-__global__ __launch_bounds__(SMV_THREADS) void dense_sandwich_matvec_kernel(
+__global__ __launch_bounds__(THREADS) void dense_sandwich_matvec_kernel(
     const F *__restrict__ X, int64_t n, int m, const F *__restrict__ u, const F *__restrict__ dm,
     const F *__restrict__ t_add, const F *__restrict__ center, const F *__restrict__ shift,
     int64_t rows_per_wg, double *__restrict__ part, F *__restrict__ w) {
@@ -53,26 +36,16 @@ __global__ __launch_bounds__(SMV_THREADS) void dense_sandwich_matvec_kernel(
     const int seg = lane / LPR;
     const int sl = lane % LPR;
 
-    // this lane's columns: (q * LPR + sl) * VEC + e
     F uu[NL][VEC], cc[NL][VEC];
     double acc[NL][VEC];
     bool live[NL];
-#pragma unroll
-    for (int q = 0; q < NL; ++q) {
-        const int j0 = (q * LPR + sl) * VEC;
-        live[q] = j0 < m;                              // m % VEC == 0: a vector is all in or all out
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            uu[q][e] = live[q] ? u[j0 + e] : F(0);
-            cc[q][e] = (live[q] && center) ? center[j0 + e] : F(0);
-            acc[q][e] = 0.0;
-        }
-    }
+    lane_columns<LPR>(m, sl, center, live, cc, acc);
+    lane_u<LPR>(m, sl, u, uu);
     const double s0 = shift ? (double)shift[0] : 0.0;
 
     const int64_t r_begin = (int64_t)blockIdx.x * rows_per_wg;
     const int64_t r_end = min(r_begin + rows_per_wg, n);
-    for (int64_t r0 = r_begin + (int64_t)wave * ROWS; r0 < r_end; r0 += (int64_t)SMV_WAVES * ROWS) {
+    for (int64_t r0 = r_begin + (int64_t)wave * ROWS; r0 < r_end; r0 += (int64_t)WAVES * ROWS) {
         vec_t x[R][NL];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -117,36 +90,14 @@ __global__ __launch_bounds__(SMV_THREADS) void dense_sandwich_matvec_kernel(
                 }
     }
 
-    // the row segments of a wave hold the same columns: fold them (fixed xor tree)
-#pragma unroll
-    for (int s = LPR; s < WAVE; s <<= 1)
-#pragma unroll
-        for (int q = 0; q < NL; ++q)
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) acc[q][e] += __shfl_xor(acc[q][e], s, 64);
-    // then the waves, one after the other
-    for (int wv = 0; wv < SMV_WAVES; ++wv) {
-        if (wave == wv && seg == 0) {
-#pragma unroll
-            for (int q = 0; q < NL; ++q)
-                if (live[q]) {
-#pragma unroll
-                    for (int e = 0; e < VEC; ++e) {
-                        const int j = (q * LPR + sl) * VEC + e;
-                        smv_red[j] = wv == 0 ? acc[q][e] : smv_red[j] + acc[q][e];
-                    }
-                }
-        }
-        __syncthreads();
-    }
-    double *dst = part + (int64_t)blockIdx.x * m;
-    for (int j = threadIdx.x; j < m; j += SMV_THREADS) dst[j] = smv_red[j];
+    fold_columns<LPR>(acc, live, smv_red);
+    store_partial(smv_red, part, m);
 }
 
 // K8d  the diagonal of the same product: acc_j += dm[r] (x_rj - c_j)^2.  K8's row walk, registers and fold without
-// the dot product (nothing crosses lanes inside the loop); the partials go through smv_reduce_kernel.
+// the dot product (nothing crosses lanes inside the loop); the partials go through the same reduce kernel.
 template <typename F, int VEC, int LPR, int NL, int R>
-__global__ __launch_bounds__(SMV_THREADS) void dense_sandwich_diag_kernel(
+__global__ __launch_bounds__(THREADS) void dense_sandwich_diag_kernel(
     const F *__restrict__ X, int64_t n, int m, const F *__restrict__ dm, const F *__restrict__ center,
     int64_t rows_per_wg, double *__restrict__ part) {
     typedef F vec_t __attribute__((ext_vector_type(VEC)));
@@ -161,20 +112,11 @@ __global__ __launch_bounds__(SMV_THREADS) void dense_sandwich_diag_kernel(
     F cc[NL][VEC];
     double acc[NL][VEC];
     bool live[NL];
-#pragma unroll
-    for (int q = 0; q < NL; ++q) {
-        const int j0 = (q * LPR + sl) * VEC;
-        live[q] = j0 < m;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            cc[q][e] = (live[q] && center) ? center[j0 + e] : F(0);
-            acc[q][e] = 0.0;
-        }
-    }
+    lane_columns<LPR>(m, sl, center, live, cc, acc);
 
     const int64_t r_begin = (int64_t)blockIdx.x * rows_per_wg;
     const int64_t r_end = min(r_begin + rows_per_wg, n);
-    for (int64_t r0 = r_begin + (int64_t)wave * ROWS; r0 < r_end; r0 += (int64_t)SMV_WAVES * ROWS) {
+    for (int64_t r0 = r_begin + (int64_t)wave * ROWS; r0 < r_end; r0 += (int64_t)WAVES * ROWS) {
         vec_t x[R][NL];
         double dr[R];
 #pragma unroll
@@ -207,120 +149,8 @@ __global__ __launch_bounds__(SMV_THREADS) void dense_sandwich_diag_kernel(
                 }
     }
 
-#pragma unroll
-    for (int s = LPR; s < WAVE; s <<= 1)
-#pragma unroll
-        for (int q = 0; q < NL; ++q)
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) acc[q][e] += __shfl_xor(acc[q][e], s, 64);
-    for (int wv = 0; wv < SMV_WAVES; ++wv) {
-        if (wave == wv && seg == 0) {
-#pragma unroll
-            for (int q = 0; q < NL; ++q)
-                if (live[q]) {
-#pragma unroll
-                    for (int e = 0; e < VEC; ++e) {
-                        const int j = (q * LPR + sl) * VEC + e;
-                        smv_red[j] = wv == 0 ? acc[q][e] : smv_red[j] + acc[q][e];
-                    }
-                }
-        }
-        __syncthreads();
-    }
-    double *dst = part + (int64_t)blockIdx.x * m;
-    for (int j = threadIdx.x; j < m; j += SMV_THREADS) dst[j] = smv_red[j];
-}
-
-// g[j] = sum over the nb partials in a fixed order (16 waves per 64 columns, fixed tree at the end)
-template <typename F>
-__global__ __launch_bounds__(1024) void smv_reduce_kernel(const double *__restrict__ part, int nb, int m,
-                                                          F *__restrict__ g) {
-    __shared__ double red[16][64];
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int j = blockIdx.x * 64 + lane;
-    double s = 0.0;
-    if (j < m)
-        for (int b = wave; b < nb; b += 16) s += part[(int64_t)b * m + j];
-    red[wave][lane] = s;
-    __syncthreads();
-    if (wave == 0 && j < m) {
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < 16; k += 4) t += (red[k][lane] + red[k + 1][lane]) + (red[k + 2][lane] + red[k + 3][lane]);
-        g[j] = (F)t;
-    }
-}
-
-template <typename F, int VEC, int LPR, int NL>
-int launch_smv(const F *X, int64_t n, int m, const F *u, const F *dm, const F *t_add, const F *center,
-               const F *shift, F *g, F *w, hipStream_t st) {
-    constexpr int R = NL >= 8 ? 1 : 8 / NL;
-    constexpr int ROWS = R * (WAVE / LPR);
-    // contiguous runs of whole wave steps, at most SMV_MAX_WG of them
-    const int64_t steps = ceil_div(n, ROWS);
-    const int64_t steps_per_wg = std::max<int64_t>(SMV_WAVES, ceil_div(steps, SMV_MAX_WG));
-    const int64_t rows_per_wg = steps_per_wg * ROWS;
-    const int nwg = (int)ceil_div(n, rows_per_wg);
-    void *ws = nullptr;
-    int rc = get_workspace((size_t)nwg * m * sizeof(double), &ws, st);
-    if (rc) return rc;
-    double *part = static_cast<double *>(ws);
-    prof_begin(st);
-    hipLaunchKernelGGL((dense_sandwich_matvec_kernel<F, VEC, LPR, NL, R>), dim3(nwg), dim3(SMV_THREADS),
-                       (size_t)m * sizeof(double), st, X, n, m, u, dm, t_add, center, shift, rows_per_wg, part, w);
-    prof_end(st);
-    TM_LAUNCH_CHECK();
-    hipLaunchKernelGGL((smv_reduce_kernel<F>), dim3((unsigned)ceil_div(m, 64)), dim3(1024), 0, st, part, nwg, m, g);
-    TM_LAUNCH_CHECK();
-    return TM_OK;
-}
-
-template <typename F, int VEC>
-int dispatch_smv(const F *X, int64_t n, int m, const F *u, const F *dm, const F *t_add, const F *center,
-                 const F *shift, F *g, F *w, hipStream_t st) {
-    const int nvec = (m + VEC - 1) / VEC;              // vectors per row
-    if (nvec <= 8) return launch_smv<F, VEC, 8, 1>(X, n, m, u, dm, t_add, center, shift, g, w, st);
-    if (nvec <= 16) return launch_smv<F, VEC, 16, 1>(X, n, m, u, dm, t_add, center, shift, g, w, st);
-    if (nvec <= 32) return launch_smv<F, VEC, 32, 1>(X, n, m, u, dm, t_add, center, shift, g, w, st);
-    if (nvec <= 64) return launch_smv<F, VEC, 64, 1>(X, n, m, u, dm, t_add, center, shift, g, w, st);
-    if (nvec <= 128) return launch_smv<F, VEC, 64, 2>(X, n, m, u, dm, t_add, center, shift, g, w, st);
-    if (nvec <= 256) return launch_smv<F, VEC, 64, 4>(X, n, m, u, dm, t_add, center, shift, g, w, st);
-    return launch_smv<F, VEC, 64, 8>(X, n, m, u, dm, t_add, center, shift, g, w, st);
-}
-
-template <typename F, int VEC, int LPR, int NL>
-int launch_sdiag(const F *X, int64_t n, int m, const F *dm, const F *center, F *out, hipStream_t st) {
-    constexpr int R = NL >= 8 ? 1 : 8 / NL;
-    constexpr int ROWS = R * (WAVE / LPR);
-    const int64_t steps = ceil_div(n, ROWS);
-    const int64_t steps_per_wg = std::max<int64_t>(SMV_WAVES, ceil_div(steps, SMV_MAX_WG));
-    const int64_t rows_per_wg = steps_per_wg * ROWS;
-    const int nwg = (int)ceil_div(n, rows_per_wg);
-    void *ws = nullptr;
-    int rc = get_workspace((size_t)nwg * m * sizeof(double), &ws, st);
-    if (rc) return rc;
-    double *part = static_cast<double *>(ws);
-    prof_begin(st);
-    hipLaunchKernelGGL((dense_sandwich_diag_kernel<F, VEC, LPR, NL, R>), dim3(nwg), dim3(SMV_THREADS),
-                       (size_t)m * sizeof(double), st, X, n, m, dm, center, rows_per_wg, part);
-    prof_end(st);
-    TM_LAUNCH_CHECK();
-    hipLaunchKernelGGL((smv_reduce_kernel<F>), dim3((unsigned)ceil_div(m, 64)), dim3(1024), 0, st, part, nwg, m, out);
-    TM_LAUNCH_CHECK();
-    return TM_OK;
-}
-
-template <typename F, int VEC>
-int dispatch_sdiag(const F *X, int64_t n, int m, const F *dm, const F *center, F *out, hipStream_t st) {
-    const int nvec = (m + VEC - 1) / VEC;
-    if (nvec <= 8) return launch_sdiag<F, VEC, 8, 1>(X, n, m, dm, center, out, st);
-    if (nvec <= 16) return launch_sdiag<F, VEC, 16, 1>(X, n, m, dm, center, out, st);
-    if (nvec <= 32) return launch_sdiag<F, VEC, 32, 1>(X, n, m, dm, center, out, st);
-    if (nvec <= 64) return launch_sdiag<F, VEC, 64, 1>(X, n, m, dm, center, out, st);
-    if (nvec <= 128) return launch_sdiag<F, VEC, 64, 2>(X, n, m, dm, center, out, st);
-    if (nvec <= 256) return launch_sdiag<F, VEC, 64, 4>(X, n, m, dm, center, out, st);
-    return launch_sdiag<F, VEC, 64, 8>(X, n, m, dm, center, out, st);
+    fold_columns<LPR>(acc, live, smv_red);
+    store_partial(smv_red, part, m);
 }
 
 }  // namespace
@@ -328,9 +158,8 @@ int dispatch_sdiag(const F *X, int64_t n, int m, const F *dm, const F *center, F
 template <typename F>
 int run_dense_sandwich_matvec(const F *X, int64_t n, int64_t m, const F *u, const F *dm, const F *t_add,
                               const F *center, const F *shift, F *g, F *w, hipStream_t st) {
-    constexpr int V = 16 / (int)sizeof(F);
     TM_REQUIRE(n >= 0 && m >= 0, "negative shape");
-    TM_REQUIRE(m <= (int64_t)WAVE * V * SMV_MAX_NL, "more columns than tm_dense_sandwich_matvec serves");
+    TM_REQUIRE(m <= max_columns(FULL_VEC<F>), "more columns than tm_dense_sandwich_matvec serves");
     TM_REQUIRE(n == 0 || m == 0 || (X && u && dm), "X, u and dm are required");
     TM_REQUIRE(m == 0 || g, "g is required");
     if (m == 0) return TM_OK;
@@ -338,21 +167,23 @@ int run_dense_sandwich_matvec(const F *X, int64_t n, int64_t m, const F *u, cons
         TM_HIP(hipMemsetAsync(g, 0, (size_t)m * sizeof(F), st));
         return TM_OK;
     }
-    const bool vec_ok = m % V == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-    // one element per load: only widths up to 512 (64 lanes x 8 loads)
-    if (!vec_ok) {
-        TM_REQUIRE(m <= (int64_t)WAVE * SMV_MAX_NL, "unaligned rows: at most 512 columns");
-        return dispatch_smv<F, 1>(X, n, (int)m, u, dm, t_add, center, shift, g, w, st);
-    }
-    return dispatch_smv<F, V>(X, n, (int)m, u, dm, t_add, center, shift, g, w, st);
+    const int vec = load_form(X, m);
+    TM_REQUIRE(vec != 0, "unaligned rows: at most 512 columns");
+    return dispatch<F>(vec, (int)m, [&](auto v, auto lpr, auto nl) {
+        constexpr int VEC = decltype(v)::value, LPR = decltype(lpr)::value, NL = decltype(nl)::value;
+        constexpr int R = rows_per_segment(NL);
+        return launch<F>(n, (int)m, 0, R * (WAVE / LPR), g, nullptr, st, [&](Geometry ge, size_t lds, double *part) {
+            hipLaunchKernelGGL((dense_sandwich_matvec_kernel<F, VEC, LPR, NL, R>), dim3(ge.nwg), dim3(THREADS), lds, st,
+                               X, n, (int)m, u, dm, t_add, center, shift, ge.rows_per_wg, part, w);
+        });
+    });
 }
 
 template <typename F>
 int run_dense_sandwich_diag(const F *X, int64_t n, int64_t m, const F *dm, const F *center, F *out,
                             hipStream_t st) {
-    constexpr int V = 16 / (int)sizeof(F);
     TM_REQUIRE(n >= 0 && m >= 0, "negative shape");
-    TM_REQUIRE(m <= (int64_t)WAVE * V * SMV_MAX_NL, "more columns than tm_dense_sandwich_diag serves");
+    TM_REQUIRE(m <= max_columns(FULL_VEC<F>), "more columns than tm_dense_sandwich_diag serves");
     TM_REQUIRE(n == 0 || m == 0 || (X && dm), "X and dm are required");
     TM_REQUIRE(m == 0 || out, "out is required");
     if (m == 0) return TM_OK;
@@ -360,12 +191,16 @@ int run_dense_sandwich_diag(const F *X, int64_t n, int64_t m, const F *dm, const
         TM_HIP(hipMemsetAsync(out, 0, (size_t)m * sizeof(F), st));
         return TM_OK;
     }
-    const bool vec_ok = m % V == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-    if (!vec_ok) {
-        TM_REQUIRE(m <= (int64_t)WAVE * SMV_MAX_NL, "unaligned rows: at most 512 columns");
-        return dispatch_sdiag<F, 1>(X, n, (int)m, dm, center, out, st);
-    }
-    return dispatch_sdiag<F, V>(X, n, (int)m, dm, center, out, st);
+    const int vec = load_form(X, m);
+    TM_REQUIRE(vec != 0, "unaligned rows: at most 512 columns");
+    return dispatch<F>(vec, (int)m, [&](auto v, auto lpr, auto nl) {
+        constexpr int VEC = decltype(v)::value, LPR = decltype(lpr)::value, NL = decltype(nl)::value;
+        constexpr int R = rows_per_segment(NL);
+        return launch<F>(n, (int)m, 0, R * (WAVE / LPR), out, nullptr, st, [&](Geometry ge, size_t lds, double *part) {
+            hipLaunchKernelGGL((dense_sandwich_diag_kernel<F, VEC, LPR, NL, R>), dim3(ge.nwg), dim3(THREADS), lds, st,
+                               X, n, (int)m, dm, center, ge.rows_per_wg, part);
+        });
+    });
 }
 
 }  // namespace tmh

@@ -80,6 +80,19 @@ def strict_f32() -> bool:
     return _STRICT_F32
 
 
+def _centre_and_shift(centers, key, u, shift):
+    """(c, shift) for the one-pass kernels (tm_dense_sandwich_matvec_*, tm_dense_glm_loss_grad_*) reading a dense
+    block centred: c = centers[key] in u's dtype (None without one), and sum(c * u) folded into shift -- the
+    kernels form (x_r - c) . u + shift, which is then x_r . u + the caller's shift.  u: the block's coefficients;
+    shift: one-element device tensor or None, returned in u's dtype."""
+    c = None if centers is None else centers.get(key)
+    if c is not None:
+        c = c.to(u.dtype).contiguous()
+        cu = (c * u).sum().reshape(1)
+        shift = cu if shift is None else shift + cu
+    return c, (None if shift is None else shift.to(u.dtype).contiguous())
+
+
 class DenseMatrix(MatrixBase):
     """Dense block.  Construct from a numpy array (kept on the host, uploaded lazily on the
     first product) or from an (n, m) torch cuda tensor (no host copy)."""
@@ -384,14 +397,8 @@ class DenseMatrix(MatrixBase):
         blk = self._smv_block()
         if blk is None:
             return None
-        c = None if centers is None else centers.get(0)
-        if c is not None:
-            c = c.to(u_full.dtype).contiguous()
-            cu = (c * u_full).sum().reshape(1)
-            shift = cu if shift is None else shift + cu
-        g, w = xd.dense_sandwich_matvec(blk, u_full.contiguous(), dm, center=c,
-                                        shift=None if shift is None else shift.to(u_full.dtype).contiguous(),
-                                        want_w=True)
+        c, shift = _centre_and_shift(centers, 0, u_full, shift)
+        g, w = xd.dense_sandwich_matvec(blk, u_full.contiguous(), dm, center=c, shift=shift, want_w=True)
         return g, w, (None if c is None else (None, c))
 
     def sandwich_matvec(self, d, u, rows=None, cols=None):
@@ -422,14 +429,9 @@ class DenseMatrix(MatrixBase):
         blk = self._smv_block()
         if blk is None:
             return None
-        c = None if centers is None else centers.get(0)
-        if c is not None:
-            c = c.to(u_full.dtype).contiguous()
-            cu = (c * u_full).sum().reshape(1)
-            shift = cu if shift is None else shift + cu
-        loss, g, eta, r, d = xd.dense_glm_loss_grad(
-            blk, u_full.contiguous(), family, y, wt, t_add=t_add, center=c,
-            shift=None if shift is None else shift.to(u_full.dtype).contiguous())
+        c, shift = _centre_and_shift(centers, 0, u_full, shift)
+        loss, g, eta, r, d = xd.dense_glm_loss_grad(blk, u_full.contiguous(), family, y, wt, t_add=t_add, center=c,
+                                                    shift=shift)
         return loss, g, eta, r, d, (None if c is None else (None, c))
 
     def glm_loss_grad(self, family, beta, y, weights=None, offset=None):

@@ -234,8 +234,9 @@ def dense_sandwich_xtv(X: DenseDev, d, v, kind, colmax=None, history=None, cente
     return out, None, xtv
 
 
-# widest block tm_dense_sandwich_matvec_* takes: 64 lanes x 8 loads of 16 bytes per row (rows 16-byte aligned),
-# of one element otherwise (csrc/sandwich_matvec.hip)
+# widest block the dense row walk (tm_dense_sandwich_matvec_*, tm_dense_sandwich_diag_*, tm_dense_glm_loss_grad_*)
+# takes: 64 lanes x 8 loads of 16 bytes per row (rows 16-byte aligned), of one element otherwise
+# (csrc/dense_rowwalk.hpp: load_form)
 SANDWICH_MATVEC_MAX_BYTES = 64 * 8 * 16
 SANDWICH_MATVEC_MAX_UNALIGNED = 64 * 8
 

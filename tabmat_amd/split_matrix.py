@@ -16,7 +16,7 @@ from scipy import sparse as sps
 
 from . import _device as D
 from .categorical_matrix import CategoricalMatrix
-from .dense_matrix import DenseMatrix
+from .dense_matrix import DenseMatrix, _centre_and_shift
 from .ext import split as xsplit
 from .ext.dense import dense_glm_loss_grad as xd_glm
 from .ext.dense import dense_sandwich_matvec as xd_smv
@@ -1207,13 +1207,8 @@ class SplitMatrix(MatrixBase):
         idx = self._full_dev_indices()[bi]
         u_D = u_full[idx].contiguous()
         t_o = self._matvec1_dev(u_full, None, skip=(bi,))
-        c = None if centers is None else centers.get(bi)
-        if c is not None:
-            c = c.to(u_full.dtype).contiguous()
-            cu = (c * u_D).sum().reshape(1)
-            shift = cu if shift is None else shift + cu
-        g_D, w = xd_smv(blk, u_D, dm, t_add=t_o, center=c,
-                        shift=None if shift is None else shift.to(u_full.dtype).contiguous(), want_w=True)
+        c, shift = _centre_and_shift(centers, bi, u_D, shift)
+        g_D, w = xd_smv(blk, u_D, dm, t_add=t_o, center=c, shift=shift, want_w=True)
         g, _ = self._transpose_matvec_dev(w, None, None, done={bi: g_D})
         return g, w, (None if c is None else (idx, c))
 
@@ -1233,13 +1228,8 @@ class SplitMatrix(MatrixBase):
         t_o = self._matvec1_dev(u_full, None, skip=(bi,))
         if t_add is not None:
             t_o += t_add
-        c = None if centers is None else centers.get(bi)
-        if c is not None:
-            c = c.to(u_full.dtype).contiguous()
-            cu = (c * u_D).sum().reshape(1)
-            shift = cu if shift is None else shift + cu
-        loss, g_D, eta, r, d = xd_glm(blk, u_D, family, y, wt, t_add=t_o, center=c,
-                                      shift=None if shift is None else shift.to(u_full.dtype).contiguous())
+        c, shift = _centre_and_shift(centers, bi, u_D, shift)
+        loss, g_D, eta, r, d = xd_glm(blk, u_D, family, y, wt, t_add=t_o, center=c, shift=shift)
         g, _ = self._transpose_matvec_dev(r, None, None, done={bi: g_D})
         return loss, g, eta, r, d, (None if c is None else (idx, c))
 
