@@ -2,7 +2,8 @@
 
     f(beta) = sum_i w_i l(y_i, eta_i) + alpha / 2 |beta|^2,      eta = X beta + offset
 
-for the gaussian, poisson, binomial and gamma families (identity, log, logit, log links).  A first-order solver does
+for the gaussian, poisson, binomial and gamma families (identity, log, logit, log links) and, with the log link,
+("tweedie", p), ("negative_binomial", theta) and "inverse_gaussian".  A first-order solver does
 nothing per iteration but evaluate f and its gradient, at the iterate and at every line-search trial, and every such
 evaluation here is ONE call
 
@@ -14,6 +15,7 @@ ridge term is the solver's.  Device vectors in, device results out; the only hos
 search branches on.
 
     python examples/glm_lbfgs.py [rows] [family]      # the design of examples/glm_irls.py
+                                                      # family: a name, tweedie:1.5, negative_binomial:0.5
 """
 from __future__ import annotations
 
@@ -42,9 +44,52 @@ def _two_loop(g, S, Y, rho):
     return -q
 
 
-def fit_glm_lbfgs(X, y, family: str = "poisson", alpha: float = 1.0, memory: int = 10, gtol: float = 1e-8,
+def parse_family(text: str):
+    """The family argument of the command line: a name ("poisson", "inverse_gaussian", ...) or name:parameter
+    ("tweedie:1.5", "negative_binomial:0.5") -> what glm_loss_grad takes."""
+    name, sep, param = text.partition(":")
+    return (name, float(param)) if sep else name
+
+
+def draw_response(family, eta, gen):
+    """y from the family at the true eta (device tensors).  tweedie with 1 < p < 2: a compound Poisson-gamma draw
+    with mean mu and variance mu^p (exact zeros included); p > 2 and "inverse_gaussian": a positive draw around mu;
+    negative binomial: a gamma-mixed Poisson with variance mu + theta mu^2.  (The gamma draws come from the global
+    generator: torch's gamma sampler takes none.)"""
+    n, kw = eta.shape[0], dict(dtype=eta.dtype, device=eta.device)
+    rand = lambda: torch.rand(n, generator=gen, **kw)          # noqa: E731
+    name, param = family if isinstance(family, tuple) else (family, None)
+    if name == "inverse_gaussian":
+        name, param = "tweedie", 3.0
+    if name == "tweedie" and param == 1:
+        name = "poisson"
+    if name == "tweedie" and param == 2:
+        name = "gamma"
+    if name == "poisson":
+        return torch.poisson(torch.exp(eta), generator=gen)
+    if name == "binomial":
+        return (rand() < torch.sigmoid(eta)).to(eta.dtype)
+    if name == "gamma" or (name == "tweedie" and param > 2):
+        return torch.exp(eta) * (0.5 + rand())
+    if name == "tweedie":
+        # N ~ Poisson(lam) gamma jumps of shape a and mean m: lam = mu^(2-p) / (2-p), a = (2-p) / (p-1), lam m = mu
+        mu = torch.exp(eta)
+        lam = mu ** (2.0 - param) / (2.0 - param)
+        cnt = torch.poisson(lam, generator=gen)
+        shape = cnt * ((2.0 - param) / (param - 1.0))
+        g = torch.distributions.Gamma(shape.clamp(min=1e-30), torch.ones_like(mu)).sample()
+        return torch.where(cnt > 0, g * (mu / lam) * ((param - 1.0) / (2.0 - param)), torch.zeros_like(mu))
+    if name == "negative_binomial":
+        k = 1.0 / param
+        lam = torch.distributions.Gamma(torch.full((n,), k, **kw), k / torch.exp(eta)).sample()
+        return torch.poisson(lam, generator=gen)
+    return eta + torch.randn(n, generator=gen, **kw)
+
+
+def fit_glm_lbfgs(X, y, family="poisson", alpha: float = 1.0, memory: int = 10, gtol: float = 1e-8,
                   maxiter: int = 500, weights=None, offset=None, callback=None):
-    """X: any tabmat_amd matrix (n, p); y (and weights, offset): device tensors (n,).  Minimises the family's half
+    """X: any tabmat_amd matrix (n, p); y (and weights, offset): device tensors (n,); family: what glm_loss_grad
+    takes (a name, ("tweedie", p), ("negative_binomial", theta)).  Minimises the family's half
     deviance + alpha / 2 |beta|^2 by L-BFGS with `memory` pairs; stops when the largest entry of the penalised
     gradient is at most gtol (or after maxiter iterations).  Returns beta as a float64 device tensor.
     callback(it, beta, f, gmax, evals) after every iteration (evals: glm_loss_grad calls so far)."""
@@ -99,7 +144,7 @@ def main():
     from tabmat_amd import synth
 
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
-    family = sys.argv[2] if len(sys.argv) > 2 else "poisson"
+    family = parse_family(sys.argv[2]) if len(sys.argv) > 2 else "poisson"
     X = synth.mixed_split(n, 128, 512, (256, 96, 32), 0.05, torch.float64, 3)
     t0 = time.perf_counter()
     X.to_device()
@@ -108,14 +153,7 @@ def main():
     gen = torch.Generator(device="cuda").manual_seed(0)
     truth = torch.randn(X.shape[1], dtype=torch.float64, device="cuda", generator=gen) * 0.02
     eta = X.matvec(truth)
-    if family == "poisson":
-        y = torch.poisson(torch.exp(eta), generator=gen)
-    elif family == "binomial":
-        y = (torch.rand(n, dtype=torch.float64, device="cuda", generator=gen) < torch.sigmoid(eta)).to(torch.float64)
-    elif family == "gamma":
-        y = torch.exp(eta) * (0.5 + torch.rand(n, dtype=torch.float64, device="cuda", generator=gen))
-    else:
-        y = eta + torch.randn(n, dtype=torch.float64, device="cuda", generator=gen)
+    y = draw_response(family, eta, gen)
     ts, ev = [], [0]
 
     def cb(it, beta, f, gmax, evals):

@@ -226,18 +226,44 @@ int tm_dense_sandwich_diag_f64(const double *X, int64_t n, int64_t m, const doub
                                double *out, void *stream);
 
 /* GLM ROW FUNCTIONS (csrc/glm.hip).  family selects mu(eta), the half unit deviance l, r = dl/deta and the
- * Fisher weight h of one row (links: identity, log, logit, log):
+ * Fisher weight h = (dmu/deta)^2 / V(mu) of one row (links: identity, log, logit, log, log, log):
  *   TM_GLM_GAUSSIAN  mu = eta                 l = (y - mu)^2 / 2                             r = mu - y          h = 1
  *   TM_GLM_POISSON   mu = exp(eta)            l = y (log y - eta) - (y - mu)                 r = mu - y          h = mu
  *   TM_GLM_BINOMIAL  mu = 1 / (1 + exp(-eta)) l = softplus(eta) - y eta + y log y            r = mu - y          h = mu (1 - mu)
  *                                                 + (1 - y) log(1 - y)
  *   TM_GLM_GAMMA     mu = exp(eta)            l = y exp(-eta) - 1 - log y + eta              r = 1 - y exp(-eta) h = 1
+ *   TM_GLM_TWEEDIE   mu = exp(eta)            l = y^(2-p) / ((1-p)(2-p)) - y a / (1-p)       r = b - y a         h = b
+ *     (param p)                                   + b / (2-p)
+ *                    with a = exp((1-p) eta) = mu^(1-p), b = exp((2-p) eta) = mu^(2-p), y^(2-p) = exp((2-p) log y) and
+ *                    the first term of l 0 at y = 0.  V(mu) = mu^p; 1 < p < 2 (y >= 0: compound Poisson-gamma) or
+ *                    p > 2 (y > 0; p = 3 is the inverse Gaussian).  p = 1 and p = 2 are TM_GLM_POISSON and TM_GLM_GAMMA.
+ *   TM_GLM_NEGATIVE_BINOMIAL (param theta > 0, V(mu) = mu + theta mu^2, y >= 0)
+ *                    mu = exp(eta)            l = y (log y - eta) - (y + 1/theta)            r = (mu - y) / (1 + theta mu)
+ *                                                 (log(1 + theta y) - log(1 + theta mu))     h = mu / (1 + theta mu)
+ *                    evaluated as written while theta mu <= 1 and from e = exp(-eta) beyond (r = (1 - y e) / (e + theta),
+ *                    h = 1 / (e + theta), log(1 + theta mu) = eta + log(theta + e)), so l, r and h are finite wherever
+ *                    eta is although mu overflows; log(1 + x) carries the first-order correction of the rounding of
+ *                    1 + x, so a small theta does not amplify it by 1 / theta.
  * with 0 log 0 = 0, softplus(eta) = max(eta, 0) + log1p(exp(-|eta|)) and mu (1 - mu) from the same exp(-|eta|).
  * The math runs in float64 for both data types; eta is not clamped (overflow gives inf) and the domains of y
  * (y >= 0, 0 <= y <= 1, y > 0) are the caller's contract.  With weights wt (NULL = 1) the outputs are
  * r[i] = wt[i] r_i, d[i] = wt[i] h_i and loss[0] = sum_i wt[i] l_i; a row with wt[i] == 0 gives exactly 0 in all
- * three whatever its eta (the zero is selected, not multiplied: zero weights are a row mask). */
-enum { TM_GLM_GAUSSIAN = 0, TM_GLM_POISSON = 1, TM_GLM_BINOMIAL = 2, TM_GLM_GAMMA = 3 };
+ * three whatever its eta (the zero is selected, not multiplied: zero weights are a row mask).
+ * The two families with a parameter are served by the *_p entry points only (`const double *param` after `family`: a
+ * HOST pointer to one double, p or theta, read during the call -- the one pointer of this header that is not device
+ * memory; its derived constants reach the kernels as arguments); the parameter-free entry points return TM_EINVAL for
+ * them.  The *_p entry points take every family: for the first four param is ignored (NULL is fine) and the result
+ * is bit-identical to the parameter-free entry point (the same kernels).  TM_EINVAL, before any launch, for an unknown
+ * family, a NULL param with Tweedie or the negative binomial, a Tweedie *param that is not finite or not in
+ * (1, 2) or (2, inf), a negative-binomial param that is not finite or <= 0. */
+enum {
+    TM_GLM_GAUSSIAN = 0,
+    TM_GLM_POISSON = 1,
+    TM_GLM_BINOMIAL = 2,
+    TM_GLM_GAMMA = 3,
+    TM_GLM_TWEEDIE = 4,
+    TM_GLM_NEGATIVE_BINOMIAL = 5
+};
 
 /* K9: GLM loss, gradient slice and Hessian weights from ONE pass over a C-ordered (row-major) block:
  *   eta[i] = (X[i,:] - center) . u + shift[0] + t_add[i]     (r, d, loss) = the family's row function of eta, y, wt
@@ -254,6 +280,14 @@ int tm_dense_glm_loss_grad_f32(const float *X, int64_t n, int64_t m, const float
 int tm_dense_glm_loss_grad_f64(const double *X, int64_t n, int64_t m, const double *u, int family, const double *y,
                                const double *wt, const double *t_add, const double *center, const double *shift,
                                double *g, double *eta, double *r, double *d, double *loss, void *stream);
+int tm_dense_glm_loss_grad_p_f32(const float *X, int64_t n, int64_t m, const float *u, int family, const double *param,
+                                 const float *y, const float *wt, const float *t_add, const float *center,
+                                 const float *shift, float *g, float *eta, float *r, float *d, double *loss,
+                                 void *stream);
+int tm_dense_glm_loss_grad_p_f64(const double *X, int64_t n, int64_t m, const double *u, int family, const double *param,
+                                 const double *y, const double *wt, const double *t_add, const double *center,
+                                 const double *shift, double *g, double *eta, double *r, double *d, double *loss,
+                                 void *stream);
 
 /* The same row function on an existing eta (length n) in one streaming launch: r, d (length n) and loss[0] are
  * overwritten; the loss is summed in a fixed order (no atomics).  For matrices K9 does not take (no dense
@@ -262,6 +296,10 @@ int tm_glm_rowfn_f32(int family, const float *eta, const float *y, const float *
                      double *loss, void *stream);
 int tm_glm_rowfn_f64(int family, const double *eta, const double *y, const double *wt, int64_t n, double *r,
                      double *d, double *loss, void *stream);
+int tm_glm_rowfn_p_f32(int family, const double *param, const float *eta, const float *y, const float *wt, int64_t n,
+                       float *r, float *d, double *loss, void *stream);
+int tm_glm_rowfn_p_f64(int family, const double *param, const double *eta, const double *y, const double *wt, int64_t n,
+                       double *r, double *d, double *loss, void *stream);
 
 /* X' diag(d) X of an unrestricted, 16-byte aligned, C-ordered FLOAT32 block of m = 4 k <= 256 columns
  * on the bf16 matrix cores: every element of diag(sqrt|d|) X is split into three bf16 pieces (24

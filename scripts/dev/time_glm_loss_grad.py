@@ -22,7 +22,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 
-FAMILIES = ("gaussian", "poisson", "binomial", "gamma")
+FAMILIES = ("gaussian", "poisson", "binomial", "gamma", ("tweedie", 1.5), ("negative_binomial", 1.0))
 OUT = []
 
 
@@ -45,7 +45,8 @@ def wall(fn, reps):
 
 
 def composition(X, family, beta, y):
-    """(loss, grad, eta, d) the way the parent commit's callers wrote it (examples/glm_newton_cg.py:30-34, 72-76)."""
+    """(loss, grad, eta, d) the way the parent commit's callers wrote it (examples/glm_newton_cg.py:30-34, 72-76);
+    the same spelling for tweedie and the negative binomial."""
     import torch
 
     eta = X.matvec(beta)
@@ -62,10 +63,23 @@ def composition(X, family, beta, y):
         mu = torch.sigmoid(eta)
         loss = (torch.nn.functional.softplus(eta) - y * eta).sum(dtype=torch.float64)
         r, d = mu - y, mu * (1 - mu)
-    else:
+    elif family == "gamma":
         ye = y * torch.exp(-eta.clamp(min=-30.0))
         loss = (ye - 1 - torch.log(y) + eta).sum(dtype=torch.float64)
         r, d = 1 - ye, torch.ones_like(eta)
+    elif family[0] == "tweedie":
+        p = family[1]
+        ec = eta.clamp(min=-30.0, max=30.0)
+        a, b = torch.exp((1 - p) * ec), torch.exp((2 - p) * ec)
+        ypow = torch.where(y > 0, y ** (2 - p), torch.zeros_like(y))
+        loss = (ypow / ((1 - p) * (2 - p)) - y * a / (1 - p) + b / (2 - p)).sum(dtype=torch.float64)
+        r, d = b - y * a, b
+    else:
+        th = family[1]
+        mu = torch.exp(eta.clamp(max=30.0))
+        den = 1 + th * mu
+        loss = (torch.xlogy(y, y) - y * eta - (y + 1 / th) * (torch.log1p(th * y) - torch.log1p(th * mu))).sum(dtype=torch.float64)
+        r, d = (mu - y) / den, mu / den
     return loss, X.transpose_matvec(r.contiguous()), eta, d
 
 
@@ -78,6 +92,12 @@ def draw_y(family, eta, gen):
         return (torch.rand(eta.shape, dtype=eta.dtype, device=eta.device, generator=gen) < torch.sigmoid(eta)).to(eta.dtype)
     if family == "gamma":
         return torch.exp(eta) * (0.5 + torch.rand(eta.shape, dtype=eta.dtype, device=eta.device, generator=gen))
+    if isinstance(family, tuple):
+        # tweedie (1 < p < 2): 30 % exact zeros, positive otherwise; negative binomial: counts
+        if family[0] == "negative_binomial":
+            return torch.poisson(torch.exp(eta), generator=gen)
+        u = torch.rand(eta.shape, dtype=eta.dtype, device=eta.device, generator=gen)
+        return torch.where(u < 0.3, torch.zeros_like(eta), torch.exp(eta) * (0.5 + u))
     return eta + torch.randn(eta.shape, dtype=eta.dtype, device=eta.device, generator=gen)
 
 
@@ -107,7 +127,7 @@ def abc(title, mat, rounds=8):
             for k, fn in runs.items():
                 res[k] += wall(fn, 2)
         a, b, c = (np.asarray(res[k]) for k in runs)
-        say(f"  {family}")
+        say(f"  {family if isinstance(family, str) else '%s(%g)' % family}")
         for k, ts in res.items():
             say(f"    {k:36s} {min(ts):7.3f} / {float(np.median(ts)):7.3f}")
         say(f"    fused / composition (median) = {np.median(a) / np.median(b):.3f};  fused / sandwich_matvec (median) = "
@@ -160,24 +180,29 @@ def resources():
                     cur[m.group(1)] = int(m.group(3))
     rows = {}
     for name, v in table.items():
+        # (the row function is the last template argument of K9 and of glm_rowfn: GlmRow, or GlmRowP = Tweedie / NB)
         m = re.search(r"\d+dense_(glm_loss_grad|sandwich_matvec|sandwich_diag)_kernelI([fd])Li(\d+)ELi(\d+)ELi(\d+)ELi(\d+)", name)
         if m:
             key = ("f32" if m.group(2) == "f" else "f64", int(m.group(3)), int(m.group(4)), int(m.group(5)), int(m.group(6)))
-            rows.setdefault(key, {})[{"glm_loss_grad": "K9", "sandwich_matvec": "K8", "sandwich_diag": "K8d"}[m.group(1)]] = v
+            kern = {"glm_loss_grad": "K9", "sandwich_matvec": "K8", "sandwich_diag": "K8d"}[m.group(1)]
+            rows.setdefault(key, {})[kern + ("p" if "GlmRowP" in name else "")] = v
         m = re.search(r"\d+glm_rowfn_kernelI([fd])Li(\d+)", name)
         if m:
-            rows[("f32" if m.group(1) == "f" else "f64", int(m.group(2)), 0, 0, 0)] = {"rowfn": v}
+            key = ("f32" if m.group(1) == "f" else "f64", int(m.group(2)), 0, 0, 0)
+            rows.setdefault(key, {})["rowfnp" if "GlmRowP" in name else "rowfn"] = v
     say("== registers, scratch and waves per SIMD (hipcc -Rpass-analysis=kernel-resource-usage, gfx950) ==")
-    say("  layout                           K9: vgpr scratch waves      K8: vgpr scratch waves     K8d: vgpr scratch waves")
+    say("  K9 / glm_rowfn: gaussian, poisson, binomial, gamma;  K9p / second glm_rowfn column: tweedie, negative_binomial")
+    say("  layout                           K9: vgpr scratch waves     K9p: vgpr scratch waves      K8: vgpr scratch waves"
+        "     K8d: vgpr scratch waves")
     for key in sorted(rows):
         dt, vec, lpr, nl, r = key
         v = rows[key]
         if "rowfn" in v:
-            k = v["rowfn"]
-            say(f"  glm_rowfn {dt} VEC={vec}:              {k['VGPRs']:8d} {k['ScratchSize']:7d} {k['Occupancy']:5d}")
+            say(f"  glm_rowfn {dt} VEC={vec}:      " + "".join(
+                f"        {k['VGPRs']:8d} {k['ScratchSize']:7d} {k['Occupancy']:5d}" for k in (v["rowfn"], v["rowfnp"])))
             continue
         say(f"  {dt} VEC={vec} LPR={lpr:2d} NL={nl} R={r}" + "".join(
-            f"        {k['VGPRs']:8d} {k['ScratchSize']:7d} {k['Occupancy']:5d}" for k in (v["K9"], v["K8"], v["K8d"])))
+            f"        {k['VGPRs']:8d} {k['ScratchSize']:7d} {k['Occupancy']:5d}" for k in (v["K9"], v["K9p"], v["K8"], v["K8d"])))
 
 
 def main():

@@ -2,7 +2,7 @@
 // function as a streaming kernel over an existing eta.
 //
 //   eta_r = (x_r - c) . u + shift + t_add[r]           (c, shift, t_add optional)
-//   (l_r, r_r, h_r) = the family's row function of (eta_r, y_r)          (glm_row below, float64)
+//   (l_r, r_r, h_r) = the family's row function of (eta_r, y_r)          (GlmRow / GlmRowP below, float64)
 //   r[r] = wt_r r_r     d[r] = wt_r h_r     loss = sum_r wt_r l_r     g = sum_r (x_r - c) wt_r r_r
 //
 // The row walk is the shared one (dense_rowwalk.hpp): a wave loads R rows per lane segment into registers, reduces
@@ -15,6 +15,8 @@
 //
 // Sums are fixed-order: per-workgroup partials of g plus one loss slot, finished by a second launch.  No
 // floating-point atomics; results are bitwise reproducible.
+#include <cmath>
+
 #include "dense_rowwalk.hpp"
 #include "glm_math.hpp"
 
@@ -27,50 +29,99 @@ namespace {
 constexpr int GLM_ROWFN_MAX_WG = 1024;      // all resident at once (4 per CU): no tail of late workgroups
 
 // one row of a GLM: half unit deviance l, r = dl/deta, Fisher weight h (include/tabmat_hip.h).  `family` is
-// uniform over the launch: a scalar branch.  exp / log are the register-lean ones of glm_math.hpp.
-__device__ __forceinline__ void glm_row(int family, double eta, double y, double &l, double &r, double &h) {
-    switch (family) {
-    case TM_GLM_GAUSSIAN: {
-        r = eta - y;
-        l = 0.5 * r * r;
-        h = 1.0;
-        break;
+// uniform over the launch: a scalar branch.  exp / log are the register-lean ones of glm_math.hpp.  The row
+// function is a kernel ARGUMENT type: the four parameter-free families (GlmRow) and the two with a parameter
+// (GlmRowP) are separate instantiations, so the registers of the second set are not the first set's maximum.
+struct GlmRow {
+    int family;
+    __device__ __forceinline__ void operator()(double eta, double y, double &l, double &r, double &h) const {
+        switch (family) {
+        case TM_GLM_GAUSSIAN: {
+            r = eta - y;
+            l = 0.5 * r * r;
+            h = 1.0;
+            break;
+        }
+        case TM_GLM_POISSON: {
+            const double mu = glm_exp(eta);
+            r = mu - y;
+            l = (y > 0.0 ? y * (glm_log(y) - eta) : 0.0) - (y - mu);
+            h = mu;
+            break;
+        }
+        case TM_GLM_BINOMIAL: {
+            const double e = glm_exp(-fabs(eta));          // (0, 1]
+            const double u = 1.0 + e;
+            const double q = glm_div(1.0, u);
+            const double mu = eta >= 0.0 ? q : e * q;
+            const double z = 1.0 - y;
+            // log1p(e) = log(u) + (e - (u - 1)) / u: the rounding of 1 + e, put back to first order
+            l = fmax(eta, 0.0) + (glm_log(u) + (e - (u - 1.0)) * q) - y * eta;
+            l += y > 0.0 ? y * glm_log(y) : 0.0;
+            l += z > 0.0 ? z * glm_log(z) : 0.0;
+            r = mu - y;
+            h = e * q * q;
+            break;
+        }
+        default: {  // TM_GLM_GAMMA
+            const double ye = y * glm_exp(-eta);
+            r = 1.0 - ye;
+            l = ye - 1.0 - glm_log(y) + eta;
+            h = 1.0;
+            break;
+        }
+        }
     }
-    case TM_GLM_POISSON: {
-        const double mu = glm_exp(eta);
-        r = mu - y;
-        l = (y > 0.0 ? y * (glm_log(y) - eta) : 0.0) - (y - mu);
-        h = mu;
-        break;
-    }
-    case TM_GLM_BINOMIAL: {
-        const double e = glm_exp(-fabs(eta));          // (0, 1]
-        const double u = 1.0 + e;
-        const double q = glm_div(1.0, u);
-        const double mu = eta >= 0.0 ? q : e * q;
-        const double z = 1.0 - y;
-        // log1p(e) = log(u) + (e - (u - 1)) / u: the rounding of 1 + e, put back to first order
-        l = fmax(eta, 0.0) + (glm_log(u) + (e - (u - 1.0)) * q) - y * eta;
-        l += y > 0.0 ? y * glm_log(y) : 0.0;
-        l += z > 0.0 ? z * glm_log(z) : 0.0;
-        r = mu - y;
-        h = e * q * q;
-        break;
-    }
-    default: {  // TM_GLM_GAMMA
-        const double ye = y * glm_exp(-eta);
-        r = 1.0 - ye;
-        l = ye - 1.0 - glm_log(y) + eta;
-        h = 1.0;
-        break;
-    }
-    }
+};
+
+// log(1 + x) for x >= 0, with the rounding of u = 1 + x put back to first order (as the binomial branch does).
+// The correction is at most half an ulp of u: the bare hardware reciprocal is more than it needs.
+__device__ __forceinline__ double glm_log1p_pos(double x) {
+    const double u = 1.0 + x;
+    return glm_log(u) + (x - (u - 1.0)) * __builtin_amdgcn_rcp(u);
 }
 
+// The families with a parameter, log link.  The constants are derived from the parameter once on the host
+// (glm_param) and travel as kernel arguments: scalar registers, no memory behind them.
+//   TM_GLM_TWEEDIE            c0 = 1 - p, c1 = 2 - p, c2 = 1 / ((1 - p)(2 - p)), c3 = 1 / (1 - p), c4 = 1 / (2 - p)
+//   TM_GLM_NEGATIVE_BINOMIAL  c0 = theta, c1 = 1 / theta, c2 = max(0, -log theta): eta there is theta mu = 1
+struct GlmRowP {
+    int family;
+    double c0, c1, c2, c3, c4;
+    __device__ __forceinline__ void operator()(double eta, double y, double &l, double &r, double &h) const {
+        if (family == TM_GLM_TWEEDIE) {
+            const double a = glm_exp(c0 * eta);            // mu^(1-p)
+            const double b = glm_exp(c1 * eta);            // mu^(2-p)
+            const bool pos = y > 0.0;
+            const double ya = pos ? y * a : 0.0;           // (y = 0 against an overflowed a: 0, not NaN)
+            r = b - ya;
+            h = b;
+            l = (pos ? c2 * glm_exp(c1 * glm_log(y)) : 0.0) - c3 * ya + c4 * b;
+        } else {  // TM_GLM_NEGATIVE_BINOMIAL
+            // plain while theta mu <= 1, from e = exp(-eta) beyond (eta > c2 = max(0, -log theta)), where mu may
+            // overflow while r, h and log(1 + theta mu) do not:
+            //   eta <= c2: E = mu,  u = 1 + theta mu,  r = (mu - y) / u,    h = mu / u,  log(1 + theta mu) = log1p(theta mu)
+            //   eta >  c2: E = e,   u = theta + e,     r = (1 - y e) / u,   h = 1 / u,   log(1 + theta mu) = eta + log u
+            // (eta + log(theta + e) cancels when theta mu is small: its error would grow as eps / theta, so the
+            // switch is at theta mu = 1, not at eta = 0; one exp, one division and one log either way)
+            const bool big = eta > c2;
+            const double E = glm_exp(big ? -eta : eta);
+            const double x = c0 * E;
+            const double u = big ? c0 + E : 1.0 + x;
+            const double q = glm_div(1.0, u);
+            const double L = (big ? eta : (x - (u - 1.0)) * q) + glm_log(u);
+            r = (big ? fma(-y, E, 1.0) : E - y) * q;
+            h = (big ? 1.0 : E) * q;
+            l = (y > 0.0 ? y * (glm_log(y) - eta) : 0.0) - (y + c1) * (glm_log1p_pos(c0 * y) - L);
+        }
+    }
+};
+
 // ... with the row's weight: a zero weight SELECTS zeros (0 * inf of an overflowed row would be NaN)
-__device__ __forceinline__ void glm_row_weighted(int family, double eta, double y, bool has_w, double w, double &l,
+template <typename ROWFN>
+__device__ __forceinline__ void glm_row_weighted(const ROWFN &fn, double eta, double y, bool has_w, double w, double &l,
                                                  double &r, double &d) {
-    glm_row(family, eta, y, l, r, d);
+    fn(eta, y, l, r, d);
     if (has_w) {
         const bool zero = w == 0.0;
         l = zero ? 0.0 : w * l;
@@ -105,10 +156,11 @@ __device__ __forceinline__ double block_sum_fixed(double v, double *slot) {
 }
 
 // VEC: elements per load (16 / sizeof(F) on 16-byte aligned rows, 1 else); LPR: lanes per row (8 .. 64, a power
-// of two); NL: loads per lane and row (> 1 only with LPR = 64); R: rows per lane segment and step (<= 8).
-template <typename F, int VEC, int LPR, int NL, int R>
+// of two); NL: loads per lane and row (> 1 only with LPR = 64); R: rows per lane segment and step (<= 8); ROWFN:
+// GlmRow or GlmRowP.
+template <typename F, int VEC, int LPR, int NL, int R, typename ROWFN>
 __global__ __launch_bounds__(THREADS) void dense_glm_loss_grad_kernel(
-    const F *__restrict__ X, int64_t n, int m, const F *__restrict__ u, int family, const F *__restrict__ y,
+    const F *__restrict__ X, int64_t n, int m, const F *__restrict__ u, ROWFN fn, const F *__restrict__ y,
     const F *__restrict__ wt, const F *__restrict__ t_add, const F *__restrict__ center,
     const F *__restrict__ shift, int64_t rows_per_wg, double *__restrict__ part, F *__restrict__ eta,
     F *__restrict__ rout, F *__restrict__ dout) {
@@ -167,7 +219,7 @@ __global__ __launch_bounds__(THREADS) void dense_glm_loss_grad_kernel(
         if (ev) {
             const double t = tsel + s0 + (t_add ? (double)t_add[row_e] : 0.0);
             double le, de;
-            glm_row_weighted(family, t, (double)y[row_e], wt != nullptr, wt ? (double)wt[row_e] : 1.0, le, re, de);
+            glm_row_weighted(fn, t, (double)y[row_e], wt != nullptr, wt ? (double)wt[row_e] : 1.0, le, re, de);
             eta[row_e] = (F)t;
             rout[row_e] = (F)re;
             dout[row_e] = (F)de;
@@ -195,8 +247,8 @@ __global__ __launch_bounds__(THREADS) void dense_glm_loss_grad_kernel(
 // vector each would not cover the memory latency); one loss partial per workgroup
 constexpr int GLM_ROWFN_U = 4;
 
-template <typename F, int VEC>
-__global__ __launch_bounds__(THREADS) void glm_rowfn_kernel(int family, const F *__restrict__ eta,
+template <typename F, int VEC, typename ROWFN>
+__global__ __launch_bounds__(THREADS) void glm_rowfn_kernel(ROWFN fn, const F *__restrict__ eta,
                                                              const F *__restrict__ y, const F *__restrict__ wt,
                                                              int64_t n, F *__restrict__ rout,
                                                              F *__restrict__ dout, double *__restrict__ part) {
@@ -225,7 +277,7 @@ __global__ __launch_bounds__(THREADS) void glm_rowfn_kernel(int family, const F 
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) {
                     double l, r, d;
-                    glm_row_weighted(family, (double)ev[k][e], (double)yv[k][e], wt != nullptr,
+                    glm_row_weighted(fn, (double)ev[k][e], (double)yv[k][e], wt != nullptr,
                                      wt ? (double)wv[k][e] : 1.0, l, r, d);
                     rv[e] = (F)r;
                     dv[e] = (F)d;
@@ -240,7 +292,7 @@ __global__ __launch_bounds__(THREADS) void glm_rowfn_kernel(int family, const F 
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         for (int64_t i = nfull * VEC; i < n; ++i) {
             double l, r, d;
-            glm_row_weighted(family, (double)eta[i], (double)y[i], wt != nullptr, wt ? (double)wt[i] : 1.0, l, r, d);
+            glm_row_weighted(fn, (double)eta[i], (double)y[i], wt != nullptr, wt ? (double)wt[i] : 1.0, l, r, d);
             rout[i] = (F)r;
             dout[i] = (F)d;
             lacc += l;
@@ -251,15 +303,39 @@ __global__ __launch_bounds__(THREADS) void glm_rowfn_kernel(int family, const F 
 }
 
 inline bool glm_family_ok(int family) { return family >= TM_GLM_GAUSSIAN && family <= TM_GLM_GAMMA; }
+inline bool glm_family_has_param(int family) { return family == TM_GLM_TWEEDIE || family == TM_GLM_NEGATIVE_BINOMIAL; }
+
+// the constants of GlmRowP from the family's parameter; false for a parameter outside the family's domain
+// (Tweedie: 1 < p < 2 or p > 2; negative binomial: theta > 0; both finite)
+inline bool glm_param(int family, double param, GlmRowP &fn) {
+    if (!std::isfinite(param)) return false;
+    fn = GlmRowP{family, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (family == TM_GLM_TWEEDIE) {
+        if (!((param > 1.0 && param < 2.0) || param > 2.0)) return false;
+        fn.c0 = 1.0 - param;
+        fn.c1 = 2.0 - param;
+        fn.c2 = 1.0 / (fn.c0 * fn.c1);
+        fn.c3 = 1.0 / fn.c0;
+        fn.c4 = 1.0 / fn.c1;
+        return true;
+    }
+    if (family == TM_GLM_NEGATIVE_BINOMIAL) {
+        if (!(param > 0.0)) return false;
+        fn.c0 = param;
+        fn.c1 = 1.0 / param;
+        fn.c2 = std::max(0.0, -std::log(param));
+        return true;
+    }
+    return false;
+}
 
 }  // namespace
 
-template <typename F>
-int run_dense_glm_loss_grad(const F *X, int64_t n, int64_t m, const F *u, int family, const F *y, const F *wt,
+template <typename F, typename ROWFN>
+int run_dense_glm_loss_grad(const F *X, int64_t n, int64_t m, const F *u, const ROWFN &fn, const F *y, const F *wt,
                             const F *t_add, const F *center, const F *shift, F *g, F *eta, F *r, F *d,
                             double *loss, hipStream_t st) {
     TM_REQUIRE(n >= 0 && m >= 0, "negative shape");
-    TM_REQUIRE(glm_family_ok(family), "unknown family");
     TM_REQUIRE(m > 0, "a block without columns has no row walk: use tm_glm_rowfn");
     TM_REQUIRE(m <= max_columns(FULL_VEC<F>), "more columns than tm_dense_glm_loss_grad serves");
     TM_REQUIRE(g && loss, "g and loss are required");
@@ -275,18 +351,17 @@ int run_dense_glm_loss_grad(const F *X, int64_t n, int64_t m, const F *u, int fa
         constexpr int VEC = decltype(v)::value, LPR = decltype(lpr)::value, NL = decltype(nl)::value;
         constexpr int R = rows_per_segment(NL);
         return launch<F>(n, (int)m, 1, R * (WAVE / LPR), g, loss, st, [&](Geometry ge, size_t lds, double *part) {
-            hipLaunchKernelGGL((dense_glm_loss_grad_kernel<F, VEC, LPR, NL, R>), dim3(ge.nwg), dim3(THREADS), lds, st,
-                               X, n, (int)m, u, family, y, wt, t_add, center, shift, ge.rows_per_wg, part, eta, r, d);
+            hipLaunchKernelGGL((dense_glm_loss_grad_kernel<F, VEC, LPR, NL, R, ROWFN>), dim3(ge.nwg), dim3(THREADS), lds,
+                               st, X, n, (int)m, u, fn, y, wt, t_add, center, shift, ge.rows_per_wg, part, eta, r, d);
         });
     });
 }
 
-template <typename F>
-int run_glm_rowfn(int family, const F *eta, const F *y, const F *wt, int64_t n, F *r, F *d, double *loss,
+template <typename F, typename ROWFN>
+int run_glm_rowfn(const ROWFN &fn, const F *eta, const F *y, const F *wt, int64_t n, F *r, F *d, double *loss,
                   hipStream_t st) {
     constexpr int V = 16 / (int)sizeof(F);
     TM_REQUIRE(n >= 0, "negative length");
-    TM_REQUIRE(glm_family_ok(family), "unknown family");
     TM_REQUIRE(loss, "loss is required");
     TM_REQUIRE(n == 0 || (eta && y && r && d), "eta, y, r and d are required");
     if (n == 0) {
@@ -305,16 +380,46 @@ int run_glm_rowfn(int family, const F *eta, const F *y, const F *wt, int64_t n, 
     double *part = static_cast<double *>(ws);
     prof_begin(st);
     if (vec_ok)
-        hipLaunchKernelGGL((glm_rowfn_kernel<F, V>), dim3(nwg), dim3(THREADS), 0, st, family, eta, y, wt, n, r, d,
+        hipLaunchKernelGGL((glm_rowfn_kernel<F, V, ROWFN>), dim3(nwg), dim3(THREADS), 0, st, fn, eta, y, wt, n, r, d,
                            part);
     else
-        hipLaunchKernelGGL((glm_rowfn_kernel<F, 1>), dim3(nwg), dim3(THREADS), 0, st, family, eta, y, wt, n, r, d,
+        hipLaunchKernelGGL((glm_rowfn_kernel<F, 1, ROWFN>), dim3(nwg), dim3(THREADS), 0, st, fn, eta, y, wt, n, r, d,
                            part);
     prof_end(st);
     TM_LAUNCH_CHECK();
     hipLaunchKernelGGL((reduce_kernel<F>), dim3(1), dim3(1024), 0, st, part, nwg, 0, 1, (F *)nullptr, loss);
     TM_LAUNCH_CHECK();
     return TM_OK;
+}
+
+// the entry points: the parameter-free families run GlmRow, Tweedie and negative binomial GlmRowP.  param: a HOST
+// pointer to the family's parameter, read here (NULL from the parameter-free entry points: codes 4 and 5 are then
+// unknown families).  family and *param are checked before anything is launched.
+template <typename F>
+int dense_glm_loss_grad_entry(const F *X, int64_t n, int64_t m, const F *u, int family, const double *param,
+                              const F *y, const F *wt, const F *t_add, const F *center, const F *shift, F *g, F *eta,
+                              F *r, F *d, double *loss, void *stream) {
+    if (glm_family_has_param(family) && param) {
+        GlmRowP fn;
+        TM_REQUIRE(glm_param(family, *param, fn), "family parameter outside its domain");
+        return run_dense_glm_loss_grad<F>(X, n, m, u, fn, y, wt, t_add, center, shift, g, eta, r, d, loss,
+                                          as_stream(stream));
+    }
+    TM_REQUIRE(glm_family_ok(family), "unknown family (tweedie and negative_binomial: the *_p entry points, with param)");
+    return run_dense_glm_loss_grad<F>(X, n, m, u, GlmRow{family}, y, wt, t_add, center, shift, g, eta, r, d, loss,
+                                      as_stream(stream));
+}
+
+template <typename F>
+int glm_rowfn_entry(int family, const double *param, const F *eta, const F *y, const F *wt, int64_t n, F *r,
+                    F *d, double *loss, void *stream) {
+    if (glm_family_has_param(family) && param) {
+        GlmRowP fn;
+        TM_REQUIRE(glm_param(family, *param, fn), "family parameter outside its domain");
+        return run_glm_rowfn<F>(fn, eta, y, wt, n, r, d, loss, as_stream(stream));
+    }
+    TM_REQUIRE(glm_family_ok(family), "unknown family (tweedie and negative_binomial: the *_p entry points, with param)");
+    return run_glm_rowfn<F>(GlmRow{family}, eta, y, wt, n, r, d, loss, as_stream(stream));
 }
 
 }  // namespace tmh
@@ -324,23 +429,45 @@ extern "C" {
 int tm_dense_glm_loss_grad_f32(const float *X, int64_t n, int64_t m, const float *u, int family, const float *y,
                                const float *wt, const float *t_add, const float *center, const float *shift,
                                float *g, float *eta, float *r, float *d, double *loss, void *stream) {
-    return tmh::run_dense_glm_loss_grad<float>(X, n, m, u, family, y, wt, t_add, center, shift, g, eta, r, d, loss,
-                                               tmh::as_stream(stream));
+    return tmh::dense_glm_loss_grad_entry<float>(X, n, m, u, family, nullptr, y, wt, t_add, center, shift, g, eta,
+                                                 r, d, loss, stream);
 }
 int tm_dense_glm_loss_grad_f64(const double *X, int64_t n, int64_t m, const double *u, int family, const double *y,
                                const double *wt, const double *t_add, const double *center, const double *shift,
                                double *g, double *eta, double *r, double *d, double *loss, void *stream) {
-    return tmh::run_dense_glm_loss_grad<double>(X, n, m, u, family, y, wt, t_add, center, shift, g, eta, r, d, loss,
-                                                tmh::as_stream(stream));
+    return tmh::dense_glm_loss_grad_entry<double>(X, n, m, u, family, nullptr, y, wt, t_add, center, shift, g, eta,
+                                                  r, d, loss, stream);
+}
+int tm_dense_glm_loss_grad_p_f32(const float *X, int64_t n, int64_t m, const float *u, int family, const double *param,
+                                 const float *y, const float *wt, const float *t_add, const float *center,
+                                 const float *shift, float *g, float *eta, float *r, float *d, double *loss,
+                                 void *stream) {
+    return tmh::dense_glm_loss_grad_entry<float>(X, n, m, u, family, param, y, wt, t_add, center, shift, g, eta,
+                                                 r, d, loss, stream);
+}
+int tm_dense_glm_loss_grad_p_f64(const double *X, int64_t n, int64_t m, const double *u, int family, const double *param,
+                                 const double *y, const double *wt, const double *t_add, const double *center,
+                                 const double *shift, double *g, double *eta, double *r, double *d, double *loss,
+                                 void *stream) {
+    return tmh::dense_glm_loss_grad_entry<double>(X, n, m, u, family, param, y, wt, t_add, center, shift, g,
+                                                  eta, r, d, loss, stream);
 }
 
 int tm_glm_rowfn_f32(int family, const float *eta, const float *y, const float *wt, int64_t n, float *r, float *d,
                      double *loss, void *stream) {
-    return tmh::run_glm_rowfn<float>(family, eta, y, wt, n, r, d, loss, tmh::as_stream(stream));
+    return tmh::glm_rowfn_entry<float>(family, nullptr, eta, y, wt, n, r, d, loss, stream);
 }
 int tm_glm_rowfn_f64(int family, const double *eta, const double *y, const double *wt, int64_t n, double *r,
                      double *d, double *loss, void *stream) {
-    return tmh::run_glm_rowfn<double>(family, eta, y, wt, n, r, d, loss, tmh::as_stream(stream));
+    return tmh::glm_rowfn_entry<double>(family, nullptr, eta, y, wt, n, r, d, loss, stream);
+}
+int tm_glm_rowfn_p_f32(int family, const double *param, const float *eta, const float *y, const float *wt, int64_t n,
+                       float *r, float *d, double *loss, void *stream) {
+    return tmh::glm_rowfn_entry<float>(family, param, eta, y, wt, n, r, d, loss, stream);
+}
+int tm_glm_rowfn_p_f64(int family, const double *param, const double *eta, const double *y, const double *wt, int64_t n,
+                       double *r, double *d, double *loss, void *stream) {
+    return tmh::glm_rowfn_entry<double>(family, param, eta, y, wt, n, r, d, loss, stream);
 }
 
 }  // extern "C"

@@ -424,8 +424,8 @@ class DenseMatrix(MatrixBase):
 
     def _glm_dev(self, family, u_full, y, wt, t_add, shift=None, centers=None):
         """SplitMatrix._glm_dev for a lone dense block: (loss, g, eta, r, d, fix) from one pass
-        (tm_dense_glm_loss_grad_*), or None when the kernel does not take the block.  centers: {0: column centres}
-        or None."""
+        (tm_dense_glm_loss_grad_*), or None when the kernel does not take the block.  family: the resolved
+        (code, param) of _glm_args; centers: {0: column centres} or None."""
         blk = self._smv_block()
         if blk is None:
             return None

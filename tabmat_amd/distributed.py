@@ -199,7 +199,8 @@ class RowShardedMatrix:
 
     def glm_loss_grad(self, family, beta, y, weights=None, offset=None):
         """(loss, grad, eta, d) of the whole matrix's GLM at beta: beta replicated on every rank, y / weights /
-        offset the LOCAL slices.  The local gradient and loss are packed into one float64 buffer and summed with
+        offset the LOCAL slices.  family goes to the local matrix as it is: a name, ("tweedie", p),
+        ("negative_binomial", theta) or "inverse_gaussian" (MatrixBase.glm_loss_grad).  The local gradient and loss are packed into one float64 buffer and summed with
         ONE all-reduce; eta and d stay local (they are row-partitioned, like matvec).  loss comes back as the
         local call returns it: a Python float for numpy inputs, a 0-dim float64 device tensor else."""
         loss, g, eta, d = self._glm(family, beta, y, weights, offset)

@@ -283,14 +283,78 @@ def dense_sandwich_diag(X: DenseDev, dm, center=None):
 
 
 # family names of glm_loss_grad -> the TM_GLM_* codes of include/tabmat_hip.h
-GLM_FAMILIES = {"gaussian": 0, "poisson": 1, "binomial": 2, "gamma": 3}
+GLM_FAMILIES = {"gaussian": 0, "poisson": 1, "binomial": 2, "gamma": 3, "tweedie": 4, "negative_binomial": 5}
+# the families that come with a parameter, ("tweedie", p) / ("negative_binomial", theta), and the parameter's name
+GLM_FAMILY_PARAMS = {"tweedie": "p", "negative_binomial": "theta"}
+# other spellings of a (family, parameter) pair
+GLM_FAMILY_ALIASES = {"inverse_gaussian": ("tweedie", 3.0)}
 
 
-def dense_glm_loss_grad(X: DenseDev, u, family: int, y, wt=None, t_add=None, center=None, shift=None):
+def resolve_glm_family(family):
+    """(code, param) of a glm_loss_grad family: a GLM_FAMILIES name, ("tweedie", p) with 1 < p < 2 or p > 2,
+    ("negative_binomial", theta) with theta > 0, or "inverse_gaussian" (= ("tweedie", 3.0)).  param is 0.0 for the
+    families without one.  ("tweedie", 1) and ("tweedie", 2) are poisson and gamma (the same model under the log
+    link).  ValueError for anything else -- a parameterised family without its parameter included."""
+    import math
+
+    spelled = family
+    if isinstance(family, str) and family in GLM_FAMILY_ALIASES:
+        family = GLM_FAMILY_ALIASES[family]
+    known = sorted(GLM_FAMILIES) + sorted(GLM_FAMILY_ALIASES)
+    if isinstance(family, str):
+        if family not in GLM_FAMILIES:
+            raise ValueError(f"unknown family {spelled!r}; glm_loss_grad knows {known}")
+        if family in GLM_FAMILY_PARAMS:
+            pn = GLM_FAMILY_PARAMS[family]
+            raise ValueError(f"family {family!r} needs its parameter {pn}: pass ({family!r}, {pn})")
+        return GLM_FAMILIES[family], 0.0
+    if not isinstance(family, tuple):
+        raise ValueError(f"unknown family {spelled!r}; glm_loss_grad knows {known}")
+    if not family or not isinstance(family[0], str) or family[0] not in GLM_FAMILIES:
+        raise ValueError(f"unknown family {spelled!r}; glm_loss_grad knows {known}")
+    name = family[0]
+    if name not in GLM_FAMILY_PARAMS:
+        raise ValueError(f"family {name!r} takes no parameter: pass {name!r}, not {spelled!r}")
+    pn = GLM_FAMILY_PARAMS[name]
+    if len(family) != 2:
+        raise ValueError(f"family {spelled!r}: {name!r} needs exactly its parameter {pn}, as ({name!r}, {pn})")
+    try:
+        param = float(family[1])
+    except (TypeError, ValueError):
+        raise ValueError(f"family {spelled!r}: the parameter {pn} must be a number") from None
+    if not math.isfinite(param):
+        raise ValueError(f"family {spelled!r}: the parameter {pn} must be finite")
+    if name == "tweedie":
+        if param == 1.0:
+            return GLM_FAMILIES["poisson"], 0.0
+        if param == 2.0:
+            return GLM_FAMILIES["gamma"], 0.0
+        if not (1.0 < param < 2.0 or param > 2.0):
+            raise ValueError(f"family {spelled!r}: glm_loss_grad serves tweedie with 1 <= p <= 2 or p > 2")
+    elif not param > 0.0:
+        raise ValueError(f"family {spelled!r}: theta must be > 0")
+    return GLM_FAMILIES[name], param
+
+
+def _glm_symbol(stem: str, family, suffix: str):
+    """(symbol, leading family arguments) for a resolved family -- (code, param) or a bare code: the parameter-free
+    entry point for the families without a parameter, the _p one for the others.  There param follows family as a
+    HOST pointer to one double (a ctypes c_double passed by reference: it lives until the call returns)."""
+    import ctypes as C
+
+    code, param = family if isinstance(family, tuple) else (family, 0.0)
+    code = int(code)
+    if code in (GLM_FAMILIES[k] for k in GLM_FAMILY_PARAMS):
+        return f"{stem}_p_{suffix}", (code, C.byref(C.c_double(float(param))))
+    return f"{stem}_{suffix}", (code,)
+
+
+def dense_glm_loss_grad(X: DenseDev, u, family, y, wt=None, t_add=None, center=None, shift=None):
     """(loss, g, eta, r, d) from ONE pass over a C-ordered block (tm_dense_glm_loss_grad_*): eta = (X - 1 center') u +
     shift + t_add, (r, d, loss) the family's weighted row function of (eta, y, wt), g = (X - 1 center')' r.  family:
-    a GLM_FAMILIES code; u, center: length X.m; y, wt, t_add: length X.n; shift: a one-element device tensor; all
-    of the block's dtype; wt / t_add / center / shift may be None.  loss: 0-dim float64 device tensor."""
+    (code, param) as resolve_glm_family gives it, or a bare GLM_FAMILIES code (tweedie and negative_binomial run
+    tm_dense_glm_loss_grad_p_*); u, center: length X.m; y, wt, t_add: length X.n; shift: a one-element device tensor;
+    all of the block's dtype; wt / t_add / center / shift may be None.  loss: 0-dim float64 device tensor."""
     import torch
 
     g = D.out_buf((X.m,), X.dtype)
@@ -303,15 +367,17 @@ def dense_glm_loss_grad(X: DenseDev, u, family: int, y, wt=None, t_add=None, cen
         assert v is None or (v.numel() == X.n and v.is_contiguous())
     assert center is None or (center.numel() == X.m and center.is_contiguous())
     assert shift is None or shift.numel() == 1
-    call(f"tm_dense_glm_loss_grad_{D.fsuf(X.buf)}", D.p(X.buf), X.n, X.m, D.p(u), int(family), D.p(y), D.p(wt),
-         D.p(t_add), D.p(center), D.p(shift), D.p(g), D.p(eta), D.p(r), D.p(d), D.p(loss), D.stream_ptr())
+    sym, fam = _glm_symbol("tm_dense_glm_loss_grad", family, D.fsuf(X.buf))
+    call(sym, D.p(X.buf), X.n, X.m, D.p(u), *fam, D.p(y), D.p(wt), D.p(t_add), D.p(center), D.p(shift), D.p(g),
+         D.p(eta), D.p(r), D.p(d), D.p(loss), D.stream_ptr())
     return loss, g, eta, r, d
 
 
-def glm_rowfn(family: int, eta, y, wt=None):
+def glm_rowfn(family, eta, y, wt=None):
     """(loss, r, d): the family's weighted row function of an existing eta in one streaming launch
-    (tm_glm_rowfn_*; the device function K9 evaluates).  eta, y, wt (or None): 1-D device tensors of one float
-    dtype and length; loss: 0-dim float64 device tensor."""
+    (tm_glm_rowfn_*, tm_glm_rowfn_p_* for tweedie and negative_binomial; the device function K9 evaluates).
+    family: (code, param) or a bare code, as in dense_glm_loss_grad.  eta, y, wt (or None): 1-D device tensors of
+    one float dtype and length; loss: 0-dim float64 device tensor."""
     import torch
 
     D.same_float("glm_rowfn", eta, y, wt)
@@ -320,6 +386,6 @@ def glm_rowfn(family: int, eta, y, wt=None):
     assert wt is None or (wt.numel() == n and wt.is_contiguous())
     r, d = D.out_buf((n,), eta.dtype), D.out_buf((n,), eta.dtype)
     loss = D.out_buf((), torch.float64)
-    call(f"tm_glm_rowfn_{D.fsuf(eta)}", int(family), D.p(eta), D.p(y), D.p(wt), n, D.p(r), D.p(d), D.p(loss),
-         D.stream_ptr())
+    sym, fam = _glm_symbol("tm_glm_rowfn", family, D.fsuf(eta))
+    call(sym, *fam, D.p(eta), D.p(y), D.p(wt), n, D.p(r), D.p(d), D.p(loss), D.stream_ptr())
     return loss, r, d

@@ -64,7 +64,10 @@ class MatrixBase(ABC):
 
     def glm_loss_grad(self, family, beta, y, weights=None, offset=None):
         """(loss, grad, eta, d) of a GLM at beta -- what a solver needs at every iterate and line-search trial.
-        family: "gaussian", "poisson", "binomial" or "gamma" (links: identity, log, logit, log).  With
+        family: "gaussian", "poisson", "binomial" or "gamma" (links: identity, log, logit, log), or with the log link
+        ("tweedie", p) for 1 <= p <= 2 or p > 2 (p = 1 / 2 are poisson / gamma), "inverse_gaussian" (= ("tweedie", 3.0))
+        and ("negative_binomial", theta) with variance mu + theta mu^2, theta > 0; the bare names "tweedie" and
+        "negative_binomial", a parameter outside these ranges or a malformed tuple raise ValueError.  With
         eta = self @ beta + offset, w = weights (1 when None) and the family's half unit deviance l, r = dl/deta
         and Fisher weight h per row (include/tabmat_hip.h): loss = sum w l (half the deviance, summed in float64),
         grad = self' (w r) (its gradient in beta), d = w h (ready for sandwich / sandwich_matvec /
@@ -324,13 +327,12 @@ class _GlmArgs:
 
 
 def _glm_args(mat, family, beta, y, weights, offset):
-    """Host-side checks of glm_loss_grad (no device work): a known family, beta 1-D of length p, y / weights /
-    offset 1-D of length n."""
+    """Host-side checks of glm_loss_grad (no device work): a known family with a valid parameter (resolved to
+    (code, param): a.family), beta 1-D of length p, y / weights / offset 1-D of length n."""
     from . import _device as D
-    from .ext.dense import GLM_FAMILIES
+    from .ext.dense import resolve_glm_family
 
-    if not isinstance(family, str) or family not in GLM_FAMILIES:
-        raise ValueError(f"unknown family {family!r}; glm_loss_grad knows {sorted(GLM_FAMILIES)}")
+    family = resolve_glm_family(family)     # (code, param); ValueError for a family glm_loss_grad does not know
     n, p = mat.shape
     on_dev = D.is_dev(beta)
     if not on_dev:
@@ -350,7 +352,7 @@ def _glm_args(mat, family, beta, y, weights, offset):
             if v.ndim != 1 or v.shape[0] != n:
                 raise ValueError(f"{name} has shape {tuple(v.shape)}; glm_loss_grad needs length {n} (the rows)")
         vecs[name] = v
-    return _GlmArgs(mat=mat, family=GLM_FAMILIES[family], beta=beta, n=n, p=p, on_dev=on_dev,
+    return _GlmArgs(mat=mat, family=family, beta=beta, n=n, p=p, on_dev=on_dev,
                     dtype=np.dtype(mat.dtype), **vecs)
 
 

@@ -1217,7 +1217,8 @@ class SplitMatrix(MatrixBase):
         dense block takes the fused pass (or the matrix runs in row parts).  As _smv_dev: the other blocks'
         X_b u_b comes first and t_add (the offset) is added to it; one pass over the fused dense block D
         (tm_dense_glm_loss_grad_*) then gives eta = X_D u_D + that + shift, the family's r, d and loss, and
-        g_D = X_D' r; the other blocks' transpose_matvec runs on r.  centers / shift / fix as in _smv_dev."""
+        g_D = X_D' r; the other blocks' transpose_matvec runs on r.  family: the resolved (code, param) of _glm_args;
+        centers / shift / fix as in _smv_dev."""
         bi = self._smv_dense_block()
         if bi is None or self._parts() is not None:
             return None
