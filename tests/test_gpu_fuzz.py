@@ -12,10 +12,15 @@ from scipy import sparse as sps
 pytestmark = pytest.mark.gpu
 
 
-def _random_split(rng, dtype):
+N_CHOICES = (1, 7, 64, 129, 1000, 4096, 5003, 20000)
+
+
+def _random_split(rng, dtype, n_choices=N_CHOICES):
+    """(matrix, dense float64 image) of one random design; n_choices: the row counts n is drawn from (one rng call
+    whatever the list)."""
     import tabmat_amd as tm
 
-    n = int(rng.choice([1, 7, 64, 129, 1000, 4096, 5003, 20000]))
+    n = int(rng.choice(list(n_choices)))
     blocks, dense_parts = [], []
     kinds = list(rng.permutation(["dense", "sparse", "cat", "cat", "sparse", "dense"])[: rng.integers(1, 6)])
     if rng.random() < 0.3:          # a categorical-heavy design (fused pair tables, fused matvec)
