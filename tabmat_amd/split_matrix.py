@@ -2,13 +2,14 @@
 blocks (reference: /root/reference/src/tabmat/split_matrix.py).  The cross-block assembly of
 sandwich / matvec / transpose_matvec runs on ONE GPU: every block product is a HIP kernel and
 the block results are scattered into the float64 p x p (or length-p / length-n) device buffer
-by tm_scatter_block -- no host round trip inside a call."""
+by tm_scatter_block -- no host round trip inside a call.  SplitMatrix._sandwich_dev chooses the route of a
+sandwich call, _Assembly puts its block products together ("Sandwich assembly")."""
 from __future__ import annotations
 
 import os
 import warnings
 from collections.abc import Sequence
-from typing import Optional, Union
+from typing import Optional
 
 import numpy as np
 import torch
@@ -102,6 +103,224 @@ class _Xtv:
     def __init__(self, v):
         self.v = v
         self.out = {}
+
+
+def _take(c, sub):
+    """c through an optional int32 device subset."""
+    return c if sub is None else c[sub.to(torch.int64)]
+
+
+def _zeros_outside(v, cd):
+    """v with zeros outside the positions cd (int64 device tensor)."""
+    vm = torch.zeros_like(v)
+    vm[cd] = v[cd]
+    return vm
+
+
+def _row_parts(parts, rows):
+    """(a, b, part, rows rebased to the part or None) per row part, without the parts a row list leaves empty."""
+    for a, b, part in parts:
+        r = None
+        if rows is not None:
+            r64 = rows.to(torch.int64)
+            sel = r64[(r64 >= a) & (r64 < b)]
+            if sel.numel() == 0:
+                continue
+            r = (sel - a).to(torch.int32)
+        yield a, b, part, r
+
+
+class _Assembly:
+    """The block products of ONE sandwich call on their way into `out`, in line on the current stream (the "terms"
+    route of SplitMatrix._sandwich_dev, whose arguments it carries, with the blocks' device positions pos_d and
+    column subsets sub_d).  It owns what the four phases tell each other: `empty` (blocks without a selected
+    column), `done` (block pairs (i < j) that are in `out`), `cat_diag` (categorical block -> its diagonal where a
+    table gave it for free) and `diag_scattered` (categorical blocks whose diagonal is in `out` already)."""
+
+    def __init__(self, mat, d, rows, cols_host, out, pos_d, sub_d, colsum=None, center=None, xtv=None):
+        self.mat, self.d, self.rows, self.cols_host, self.out = mat, d, rows, cols_host, out
+        self.pos_d, self.sub_d, self.colsum, self.center, self.xtv = pos_d, sub_d, colsum, center, xtv
+        self.empty = [sd is not None and D.nlen(sd) == 0 for sd in sub_d]
+        self.native = d.dtype == D.torch_dtype(mat.dtype)     # d in the matrix dtype: what the fused kernels take
+        self.done = set()
+        self.cat_diag = {}
+        self.diag_scattered = set()
+
+    def run(self):
+        self.fused_cat_cross()
+        self.cat_tables()
+        self.self_terms()
+        self.cross_terms()
+        return self.out
+
+    def put(self, i, j, res, restrict=False):
+        """Block result (i, j) (restrict: over ALL columns of both blocks) into `out` and its mirror; pair done."""
+        if restrict:
+            res = CategoricalMatrix._restrict(res, self.sub_d[i], self.sub_d[j])
+        xsplit.scatter_block(res.contiguous(), self.pos_d[i], self.pos_d[j], self.out, mirror=True)
+        self.done.add((min(i, j), max(i, j)))
+
+    def offer_colsum(self, b, full):
+        """full(): X_b' d[rows] over ALL columns of block b, where it falls out of another product for free; taken
+        (through the block's column subset) only while the block's slot is free."""
+        if self.colsum is not None and self.colsum[b] is None:
+            self.colsum[b] = _take(full(), self.sub_d[b])
+
+    def put_stacked(self, ids, w, stacked, whole=False):
+        """One multi-categorical pass over block w, stacked [levels of the categoricals `ids`, columns of w]: each
+        slice is restricted, scattered (whole: the caller put the stack out in one scatter) and marked done; the
+        levels of a COMPLETE categorical C (no dropped level, no missing code: C 1 = 1) sum to X_w' d."""
+        mats, off = self.mat.matrices, 0
+        for i in ids:
+            res = stacked[off:off + mats[i].shape[1]]
+            off += mats[i].shape[1]
+            if not mats[i].drop_first and not mats[i]._has_missings:
+                self.offer_colsum(w, lambda: res.sum(dim=0))
+            if whole:
+                self.done.add((min(i, w), max(i, w)))
+            else:
+                self.put(i, w, res, restrict=True)
+
+    def fused_cat_cross(self):
+        """Categorical x dense / sparse cross terms from ONE pass over the dense / sparse block for a whole group of
+        categorical blocks (tm_multi_cat_*), instead of one pass per pair."""
+        X, mats, d, rows = self.mat, self.mat.matrices, self.d, self.rows
+        cat_ids = [i for i, m in enumerate(mats) if isinstance(m, CategoricalMatrix) and not self.empty[i]
+                   and m.shape[1] > 0]
+        budget = (128 * 1024) // 8       # LDS tiles are made of doubles for float32 data too
+        groups = X._cat_groups(cat_ids)
+        if groups:
+            d_eff = D.masked_d(d, rows)   # row restriction = masked d (excluded rows contribute 0)
+        for grp in groups:
+            cats = X._cat_args(grp)
+            total = sum(c[1] for c in cats)
+            for w, mw in enumerate(mats):
+                if self.empty[w] or mw.dtype != X.dtype or not self.native:
+                    continue
+                stacked = X._fused_cats(mw, cats, grp, d_eff, rows, total, budget, d)
+                if stacked is None:
+                    continue
+                # no column restriction: the stacked result goes out in ONE scatter (24
+                # categoricals x 2 operands were 48 launches of ~5 us)
+                whole = self.cols_host is None and len(grp) > 1
+                if whole:
+                    xsplit.scatter_block(stacked.contiguous(), X._group_pos(grp, self.pos_d), self.pos_d[w],
+                                         self.out, mirror=True)
+                self.put_stacked(grp, w, stacked, whole)
+        # categoricals with too many levels for the fused groups, against a NARROW dense block: the generic LDS-tile
+        # kernel holds [all their levels][8 columns or fewer] at once, so one pass over the block serves them all
+        # (the reference's design dense_cat: two 1000-level categoricals x 5 dense columns were two passes of 0.08 ms)
+        big = [i for i in cat_ids if mats[i].shape[1] > X.FUSED_LEVELS]
+        if 2 <= len(big) <= 16 and self.native:
+            cats = X._cat_args(big)
+            d_big = None
+            for w, mw in enumerate(mats):
+                if (self.empty[w] or not isinstance(mw, DenseMatrix) or mw.dtype != X.dtype
+                        or not xsplit.multi_cat_dense_tile_ok(cats, mw._dev_c())):
+                    continue
+                if d_big is None:
+                    d_big = D.masked_d(d, rows)
+                self.put_stacked(big, w, xsplit.multi_cat_dense_sandwich(cats, d_big, mw._dev_c()))
+
+    def cat_tables(self):
+        """Categorical x categorical tables and the categorical diagonals: all tables that fit an LDS tile in ONE
+        pass over the codes (tm_multi_cat_pairs_*: a design with k categoricals has k (k - 1) / 2 of them, one
+        launch each was ~30 us apiece), the others pair by pair."""
+        X, mats, d, rows, sub_d, empty = self.mat, self.mat.matrices, self.d, self.rows, self.sub_d, self.empty
+        # TABMAT_AMD_DETERMINISTIC: the diagonals must come from the fixed-order histogram
+        # (csrc/cat_det.hip), not from LDS-atomic tables -- no fused plan, no row-sum shortcut
+        det = _cm.DETERMINISTIC
+        plan = X._cat_pairs_plan() if CAT_PAIRS_FUSED and not det else None
+        if plan is not None and plan.n_pairs > 0 and d.dtype in (torch.float32, torch.float64) and self.native:
+            # column restriction: the full tables are accumulated, the scatter drops the unselected levels (-1)
+            pos_sel = None if self.cols_host is None else X._pairs_pos_sel(plan, self.cols_host)
+            tables = xsplit.multi_cat_pairs(plan, X._cat_args(plan.cat_ids), d, rows, self.out, pos=pos_sel)
+            for i, j, toff, li, lj, stride in plan.pairs:
+                if i != j:
+                    self.done.add((i, j))
+                elif not empty[i]:
+                    full = tables[toff:toff + (li - 1) * stride + 1:stride]
+                    if self.colsum is not None:
+                        full = _take(full, sub_d[i])
+                    self.cat_diag[i] = full.to(d.dtype)
+                    self.diag_scattered.add(i)
+        # the other tables: the diagonal of a categorical block is the row sum of its table with any COMPLETE
+        # partner (every row has exactly one level there), which saves its histogram pass
+        complete = [isinstance(m, CategoricalMatrix) and not m.drop_first and not m._has_missings
+                    and sub_d[k] is None and not empty[k] for k, m in enumerate(mats)]
+        from_pairs = DIAG_FROM_PAIRS and not det
+        for i, mi in enumerate(mats):
+            if empty[i] or not isinstance(mi, CategoricalMatrix):
+                continue
+            for j in range(i + 1, len(mats)):
+                if empty[j] or not isinstance(mats[j], CategoricalMatrix) or (i, j) in self.done:
+                    continue
+                res = mi._cross_sandwich_dev(mats[j], d, rows, sub_d[i], sub_d[j])
+                self.put(i, j, res)
+                if from_pairs and complete[j] and i not in self.cat_diag:
+                    self.cat_diag[i] = res.sum(dim=1)
+                if from_pairs and complete[i] and j not in self.cat_diag:
+                    self.cat_diag[j] = res.sum(dim=0)
+
+    def self_terms(self):
+        for i, mi in enumerate(self.mat.matrices):
+            if self.empty[i]:
+                continue
+            if isinstance(mi, CategoricalMatrix):
+                diag = self.cat_diag.get(i)
+                if diag is None:
+                    diag = mi._sandwich_diag_dev(self.d, self.rows, self.sub_d[i])
+                if self.colsum is not None:
+                    self.colsum[i] = diag          # one-hot entries are 0 / 1: C' d = diag(C' D C)
+                if i not in self.diag_scattered:
+                    xsplit.scatter_block(diag, self.pos_d[i], self.pos_d[i], self.out, diag=True)
+            else:
+                xsplit.scatter_block(self.self_product(i, mi), self.pos_d[i], self.pos_d[i], self.out)
+
+    def self_product(self, i, mi):
+        """X_i' D X_i of a dense / sparse block, one decision per kind of call: the second vector of
+        sandwich_and_transpose_matvec, then the column sums (with the centre), then the centre alone, then plain."""
+        d, rows, sub, colsum = self.d, self.rows, self.sub_d[i], self.colsum
+        dense_all = isinstance(mi, DenseMatrix) and sub is None
+        if self.xtv is not None and colsum is None and self.center is None and dense_all:
+            both = mi._sandwich_xtv_dev(d, self.xtv.v, rows)
+            if both is not None:            # X_dense' v comes out of the syrk's own pass
+                res, self.xtv.out[i] = both
+                return res
+        cen_i = self.center.get(i) if self.center is not None and isinstance(mi, DenseMatrix) else None
+        if colsum is not None and colsum[i] is None and dense_all and rows is None:
+            both = mi._sandwich_xtd_dev(d, cen_i)
+            if both is not None:            # X_dense' d comes out of the syrk's own pass (syrk_i8.hip, syrk_co.hip)
+                res, colsum[i] = both
+                if cen_i is not None:
+                    self.center.cs_centered.add(i)
+                return res
+        if cen_i is not None:
+            return mi._sandwich_dev(d, rows, sub, center=cen_i)
+        return mi._sandwich_dev(d, rows, sub)
+
+    def cross_terms(self):
+        """Every block pair no earlier phase has served, one launch per pair."""
+        mats, d, rows, sub_d, colsum = self.mat.matrices, self.d, self.rows, self.sub_d, self.colsum
+        for i, mi in enumerate(mats):
+            if self.empty[i]:
+                continue
+            for j in range(i + 1, len(mats)):
+                if self.empty[j] or (i, j) in self.done:
+                    continue
+                # sparse x dense: X_sparse' d rides along in the gather's stream loop
+                si, di = (i, j) if isinstance(mi, SparseMatrix) else (j, i)
+                if (colsum is not None and colsum[si] is None and isinstance(mats[si], SparseMatrix)
+                        and isinstance(mats[di], DenseMatrix)):
+                    box = []
+                    res = mats[si]._cross_sandwich_dev(mats[di], d, rows, sub_d[si], sub_d[di], colsum_box=box)
+                    if box:
+                        colsum[si] = box[0]
+                    if si != i:
+                        res = res.T
+                else:
+                    res = mi._cross_sandwich_dev(mats[j], d, rows, sub_d[i], sub_d[j])
+                self.put(i, j, res)
 
 
 def as_tabmat(a):
@@ -237,23 +456,40 @@ class SplitMatrix(MatrixBase):
             return self.indices, [None] * len(self.indices), self.shape[1]
         return xsplit.split_col_subsets(self, set_up_rows_or_cols(cols, self.shape[1]))
 
-    def _onehot_slab(self, cat_ids):
+    def _once(self, name, build, cat_ids=()):
+        """build() the first time (per set of categorical blocks, if it is for one); the same value ever after."""
+        cache = self.__dict__.setdefault(name, {})
         key = tuple(cat_ids)
-        cache = self.__dict__.setdefault("_onehot_cache", {})
         if key not in cache:
-            from .ext._types import onehot_slab
-
-            mats = self.matrices
-            cats = [(mats[i]._dev(), mats[i].shape[1], mats[i].drop_first) for i in cat_ids]
-            cache[key] = onehot_slab(cats, self.shape[0], D.torch_dtype(self.dtype))
+            cache[key] = build()
         return cache[key]
 
-    def _dev_idx(self, arrs):
-        return [D.idx_dev(a, torch.int64) for a in arrs]
+    def _for_cols(self, name, cols_host, build):
+        """build() for the LAST column selection (a solver repeats its active set): a new one replaces the old."""
+        key = np.asarray(cols_host).tobytes()
+        hit = self.__dict__.get(name)
+        if hit is None or hit[0] != key:
+            hit = self.__dict__[name] = (key, build())
+        return hit[1]
+
+    def _cat_args(self, cat_ids):
+        """(codes, levels, drop_first) of the categorical blocks `cat_ids`, as the tm_multi_cat_* wrappers take them."""
+        mats = self.matrices
+        return [(mats[i]._dev(), mats[i].shape[1], mats[i].drop_first) for i in cat_ids]
+
+    def _onehot_slab(self, cat_ids):
+        from .ext._types import onehot_slab
+
+        return self._once("_onehot_cache", lambda: onehot_slab(
+            self._cat_args(cat_ids), self.shape[0], D.torch_dtype(self.dtype)), cat_ids)
+
+    def _group_pos(self, grp, pos_d):
+        """Output positions of the stacked levels of the categorical group `grp` (unrestricted columns)."""
+        return self._once("_group_pos_cache", lambda: torch.cat([pos_d[i] for i in grp]), grp)
 
     def _full_dev_indices(self):
         if self._dev_indices is None:
-            self._dev_indices = self._dev_idx(self.indices)
+            self._dev_indices = [D.idx_dev(a, torch.int64) for a in self.indices]
         return self._dev_indices
 
     def to_device(self):
@@ -273,8 +509,7 @@ class SplitMatrix(MatrixBase):
         cat_ids = [i for i, m in enumerate(self.matrices)
                    if isinstance(m, CategoricalMatrix) and m.shape[1] > 0]
         for grp in self._cat_groups(cat_ids):
-            cats = [(self.matrices[i]._dev(), self.matrices[i].shape[1], self.matrices[i].drop_first)
-                    for i in grp]
+            cats = self._cat_args(grp)
             if any(isinstance(m, DenseMatrix) and not xsplit.multi_cat_dense_wide_ok(cats, m._dev_c())
                    and not xsplit.multi_cat_dense_tile_ok(cats, m._dev_c())
                    and not xsplit.cat_dense_sorted_ok(m._dev_c()) for m in self.matrices):
@@ -351,22 +586,19 @@ class SplitMatrix(MatrixBase):
         and per-block column subsets (split_matrix.py:341-349)."""
         if cols_host is None:
             return self._full_dev_indices(), [None] * len(self.indices), self.shape[1]
-        # the last selection's index arrays stay on the device: a solver repeats its active set,
-        # and the 2 uploads per block were 0.8 ms for 20 blocks
-        key = np.asarray(cols_host).tobytes()
-        hit = self.__dict__.get("_plan_cache")
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        pos, sub_cols, n_cols = self._split_col_subsets(cols_host)
-        pos_d = self._dev_idx(pos)
-        sub_d = [None if sc is None else D.idx_dev(sc) for sc in sub_cols]
-        self._cols_dev64(cols_host)
-        if CAT_PAIRS_FUSED:
-            plan = self._cat_pairs_plan()
-            if plan is not None and plan.n_pairs > 0:
-                self._pairs_pos_sel(plan, cols_host, (pos, sub_cols))    # staged here (no copies
-        self.__dict__["_plan_cache"] = (key, (pos_d, sub_d, n_cols))    # inside a graph capture)
-        return pos_d, sub_d, n_cols
+        # the last selection's index arrays stay on the device: the 2 uploads per block were 0.8 ms for 20 blocks
+        def build():
+            pos, sub_cols, n_cols = self._split_col_subsets(cols_host)
+            pos_d = [D.idx_dev(a, torch.int64) for a in pos]
+            sub_d = [None if sc is None else D.idx_dev(sc) for sc in sub_cols]
+            self._cols_dev64(cols_host)
+            if CAT_PAIRS_FUSED:
+                plan = self._cat_pairs_plan()
+                if plan is not None and plan.n_pairs > 0:      # staged here (no copies inside a graph capture)
+                    self._pairs_pos_sel(plan, cols_host, (pos, sub_cols))
+            return pos_d, sub_d, n_cols
+
+        return self._for_cols("_plan_cache", cols_host, build)
 
     def _blocks_finite(self) -> bool:
         """No stored inf / nan in any dense or sparse block (checked once per block)."""
@@ -375,27 +607,20 @@ class SplitMatrix(MatrixBase):
 
     def _cols_dev64(self, cols_host):
         """The column selection as an int64 device tensor (last selection cached)."""
-        key = np.asarray(cols_host).tobytes()
-        hit = self.__dict__.get("_cols64")
-        if hit is None or hit[0] != key:
-            hit = self.__dict__["_cols64"] = (key, D.idx_dev(cols_host, torch.int64))
-        return hit[1]
+        return self._for_cols("_cols64", cols_host, lambda: D.idx_dev(cols_host, torch.int64))
 
     def _pairs_pos_sel(self, plan, cols_host, split=None):
         """Output position of every level of the plan's categoricals under the column selection
         `cols_host` (-1: not selected), device int64; the last selection is kept."""
-        key = np.asarray(cols_host).tobytes()
-        hit = self.__dict__.get("_pos_sel")
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        pos_h, sub_h = split if split is not None else self._split_col_subsets(cols_host)[:2]
-        pf = np.full(int(plan.pstart[-1]), -1, dtype=np.int64)
-        for a, i in enumerate(plan.cat_ids):
-            if len(sub_h[i]):
-                pf[int(plan.pstart[a]) + np.asarray(sub_h[i], dtype=np.int64)] = pos_h[i]
-        t = D.to_dev(pf)
-        self.__dict__["_pos_sel"] = (key, t)
-        return t
+        def build():
+            pos_h, sub_h = split if split is not None else self._split_col_subsets(cols_host)[:2]
+            pf = np.full(int(plan.pstart[-1]), -1, dtype=np.int64)
+            for a, i in enumerate(plan.cat_ids):
+                if len(sub_h[i]):
+                    pf[int(plan.pstart[a]) + np.asarray(sub_h[i], dtype=np.int64)] = pos_h[i]
+            return D.to_dev(pf)
+
+        return self._for_cols("_pos_sel", cols_host, build)
 
     def _sandwich_xtd_dev(self, d, rows, cols_host, center=None):
         """(X' diag(d) X, X' d) restricted to rows / cols, both float64 on the device, from ONE
@@ -421,7 +646,7 @@ class SplitMatrix(MatrixBase):
                 if isinstance(mi, CategoricalMatrix):
                     full = D.zeros((mi.shape[1],), d.dtype)
                     mi._transpose_matvec_dev(d, rows, sd, full)
-                    cs = full if sd is None else full[sd.to(torch.int64)]
+                    cs = _take(full, sd)
                 else:
                     cs = mi._matvec_dev(d, rows, sd, None, True)
             elif center is not None and i in center.cs_centered:
@@ -457,32 +682,21 @@ class SplitMatrix(MatrixBase):
     def _cat_pairs_plan(self):
         """Bundling of the categorical x categorical tables for tm_multi_cat_pairs_* (None when the
         matrix has no categorical block).  Static: built once."""
-        plan = self.__dict__.get("_cp_plan", False)
-        if plan is False:
-            plan = None
-            ids = [i for i, m in enumerate(self.matrices)
-                   if isinstance(m, CategoricalMatrix) and m.shape[1] > 0]
-            if len(ids) >= 1:
-                pos = self._full_dev_indices()
-                plan = xsplit.CatPairsPlan([(i, self.matrices[i].shape[1]) for i in ids],
-                                           [pos[i] for i in ids])
-            self.__dict__["_cp_plan"] = plan
-        return plan
+        return self._once("_cp_plan", lambda: self._cat_plan(1, False))
+
+    def _cat_plan(self, at_least, diag_only):
+        ids = [i for i, m in enumerate(self.matrices) if isinstance(m, CategoricalMatrix) and m.shape[1] > 0
+               and (m.shape[0] > 0 or not diag_only)]
+        if len(ids) < at_least:
+            return None
+        pos = self._full_dev_indices()
+        return xsplit.CatPairsPlan([(i, self.matrices[i].shape[1]) for i in ids], [pos[i] for i in ids],
+                                   diag_only=diag_only)
 
     def _cat_hist_plan(self):
         """All categorical blocks' weighted histograms in one launch (transpose_matvec): the
         diagonals-only form of the pair-table plan.  None with fewer than two categoricals."""
-        plan = self.__dict__.get("_ch_plan", False)
-        if plan is False:
-            plan = None
-            ids = [i for i, m in enumerate(self.matrices)
-                   if isinstance(m, CategoricalMatrix) and m.shape[1] > 0 and m.shape[0] > 0]
-            if len(ids) >= 2:
-                pos = self._full_dev_indices()
-                plan = xsplit.CatPairsPlan([(i, self.matrices[i].shape[1]) for i in ids],
-                                           [pos[i] for i in ids], diag_only=True)
-            self.__dict__["_ch_plan"] = plan
-        return plan
+        return self._once("_ch_plan", lambda: self._cat_plan(2, True))
 
     def _fused_cats(self, mw, cats, cat_ids, d_eff, rows, total, budget, d_rows=None):
         """All categorical x `mw` cross blocks from ONE pass over `mw` (tm_multi_cat_*), stacked
@@ -524,11 +738,9 @@ class SplitMatrix(MatrixBase):
                     for mo in self.matrices)):
                 ent = mw._ent()
             if ent is not None:
-                pk_cache = self.__dict__.setdefault("_packed_codes", {})
-                key = tuple(cat_ids)
-                if key not in pk_cache:          # (static per set of categoricals: one word of tile rows per row)
-                    pk_cache[key] = xsplit.pack_codes(cats)
-                return xsplit.multi_cat_sparse_sandwich_ent(cats, d_eff, ent, pk_cache[key])
+                # (static per set of categoricals: one word of tile rows per row)
+                packed = self._once("_packed_codes", lambda: xsplit.pack_codes(cats), cat_ids)
+                return xsplit.multi_cat_sparse_sandwich_ent(cats, d_eff, ent, packed)
             return xsplit.multi_cat_sparse_sandwich(cats, d_eff, mw._slab())
         return None
 
@@ -536,58 +748,47 @@ class SplitMatrix(MatrixBase):
         """None, or [(r0, r1, SplitMatrix over rows r0 .. r1 - 1)] when a sparse block holds PART_NNZ
         nonzeros or more.  The parts are device row slices (views of the block storage); their twins
         are built per part."""
-        parts = self.__dict__.get("_row_parts", False)
-        if parts is False:
-            parts = None
-            big = [m for m in self.matrices
-                   if isinstance(m, SparseMatrix) and m._dev().data.numel() >= _spm.PART_NNZ]
-            if big:
-                n = self.shape[0]
-                lead = max(big, key=lambda m: m._dev().data.numel())
-                ptr = lead._dev().indptr
-                nnz = int(ptr[-1].item())
-                k = -(-nnz // max(1, int(0.8 * _spm.PART_NNZ)))
-                while True:
-                    targets = torch.arange(1, k, device=ptr.device, dtype=torch.int64) * nnz // k
-                    cuts = [0] + torch.searchsorted(ptr, targets).clamp_(0, n).tolist() + [n]
-                    cuts = sorted(set(int(c) for c in cuts))
-                    ok = all(int((m._dev().indptr[cuts[1:]] - m._dev().indptr[cuts[:-1]]).max().item())
-                             < _spm.PART_NNZ for m in big)
-                    if ok or k >= n:
-                        break
-                    k += 1
-                parts = [(a, b, self[a:b]) for a, b in zip(cuts[:-1], cuts[1:]) if b > a]
-            self.__dict__["_row_parts"] = parts
-        return parts
+        return self._once("_row_parts", self._build_parts)
+
+    def _build_parts(self):
+        big = [m for m in self.matrices
+               if isinstance(m, SparseMatrix) and m._dev().data.numel() >= _spm.PART_NNZ]
+        if not big:
+            return None
+        n = self.shape[0]
+        lead = max(big, key=lambda m: m._dev().data.numel())
+        ptr = lead._dev().indptr
+        nnz = int(ptr[-1].item())
+        k = -(-nnz // max(1, int(0.8 * _spm.PART_NNZ)))
+        while True:
+            targets = torch.arange(1, k, device=ptr.device, dtype=torch.int64) * nnz // k
+            cuts = [0] + torch.searchsorted(ptr, targets).clamp_(0, n).tolist() + [n]
+            cuts = sorted(set(int(c) for c in cuts))
+            ok = all(int((m._dev().indptr[cuts[1:]] - m._dev().indptr[cuts[:-1]]).max().item())
+                     < _spm.PART_NNZ for m in big)
+            if ok or k >= n:
+                break
+            k += 1
+        return [(a, b, self[a:b]) for a, b in zip(cuts[:-1], cuts[1:]) if b > a]
 
     def _sandwich_parts(self, parts, d, rows, cols_host, colsum, center=None):
         """Sum of the parts' sandwiches (and of their column sums; with `center` the column sums of the centred
         blocks are handed on RAW: a part's centred sum + centre * the part's sum of weights)."""
         out = None
-        for a, b, part in parts:
-            r = None
-            if rows is not None:
-                r64 = rows.to(torch.int64)
-                sel = r64[(r64 >= a) & (r64 < b)]
-                if sel.numel() == 0:
-                    continue
-                r = (sel - a).to(torch.int32)
+        for a, b, part, r in _row_parts(parts, rows):
             cs = [None] * len(self.matrices) if colsum is not None else None
             sub_cen = None if center is None else _Centering(center.vec)
             res = part._sandwich_dev(d[a:b], r, cols_host, None, cs, center=sub_cen)
             if sub_cen is not None:
                 center.groups = sub_cen.groups          # (the same path in every part: same selection)
             if sub_cen is not None and colsum is not None:
-                dsum = (d[a:b] if r is None else d[a:b][r.to(torch.int64)]).sum(dtype=torch.float64)
+                dsum = _take(d[a:b], r).sum(dtype=torch.float64)
                 _, sub_p, _ = self._sandwich_plan(cols_host)
                 for i in sub_cen.cs_centered:
                     # (a block the narrow path marked without a centre of its own -- sparse columns, dense
                     # blocks whose centres are all zero -- has centre 0: its centred sum IS the raw sum)
                     if cs[i] is not None and sub_cen.get(i) is not None:
-                        cv = sub_cen.get(i).to(torch.float64)
-                        if sub_p[i] is not None:
-                            cv = cv[sub_p[i].to(torch.int64)]
-                        cs[i] = cs[i].to(torch.float64) + cv * dsum
+                        cs[i] = cs[i].to(torch.float64) + _take(sub_cen.get(i).to(torch.float64), sub_p[i]) * dsum
             out = res if out is None else out + res
             if colsum is not None:
                 for i, c in enumerate(cs):
@@ -596,11 +797,9 @@ class SplitMatrix(MatrixBase):
                     elif colsum[i] is not False:
                         colsum[i] = c if colsum[i] is None else colsum[i] + c
         if colsum is not None:
-            for i, c in enumerate(colsum):
-                if c is False:
-                    colsum[i] = None
+            colsum[:] = [None if c is False else c for c in colsum]
         if out is None:
-            _, _, n_cols = self._sandwich_plan(cols_host)
+            n_cols = self._sandwich_plan(cols_host)[2]
             out = D.zeros((n_cols, n_cols), torch.float64)
         return out
 
@@ -631,19 +830,12 @@ class SplitMatrix(MatrixBase):
         return unsel <= FULL_UNSELECTED_SHARE * tot
 
     def _full_product_pays_cols(self, cols_host) -> bool:
-        key = np.asarray(cols_host).tobytes()
-        hit = self.__dict__.get("_fpp_cache")
-        if hit is None or hit[0] != key:
-            hit = self.__dict__["_fpp_cache"] = (key, self._full_product_pays(self._split_col_subsets(cols_host)[1]))
-        return hit[1]
+        return self._for_cols("_fpp_cache", cols_host,
+                              lambda: self._full_product_pays(self._split_col_subsets(cols_host)[1]))
 
     def _narrow_plan(self, cols_host):
-        """Bookkeeping of the dense-block form of a narrow column selection (see NARROW_COLS), or
-        None when it does not apply.  The last selection is cached."""
-        key = np.asarray(cols_host).tobytes()
-        hit = self.__dict__.get("_narrow_cache")
-        if hit is not None and hit[0] == key:
-            return hit[1]
+        """Bookkeeping of the dense-block form of a narrow column selection (see NARROW_COLS), "wide", or
+        None when neither applies (_sandwich_route keeps it for the last selection)."""
         nar = None
         pos_h, sub_h, n_cols = self._split_col_subsets(cols_host)
         mats = self.matrices
@@ -691,7 +883,6 @@ class SplitMatrix(MatrixBase):
                        sel=D.to_dev(sel), tmp=None, n_cols=n_cols)
         elif noncat and w > NARROW_COLS and FULL_THEN_SELECT <= 1.0 and self._full_product_pays(sub_h):
             nar = "wide"
-        self.__dict__["_narrow_cache"] = (key, nar)
         return nar
 
     def _sandwich_narrow(self, nar, d, rows, colsum, center=None):
@@ -747,217 +938,69 @@ class SplitMatrix(MatrixBase):
         sel = nar["sel"]
         return full.index_select(0, sel).index_select(1, sel)
 
+    def _sandwich_route(self, d, cols_host, plan):
+        """(name, bookkeeping) of the way one sandwich call is computed.  "full_then_select": at least
+        FULL_THEN_SELECT of the columns, and little wasted (_full_product_pays).  "parts": the sum over _parts().
+        "wide": more selected dense + sparse columns than "narrow" takes -- the generic restricted kernels stream
+        everything and cost the full product or more (3.35-3.7 vs 3.5 ms at 2M rows, profiles/r3_cols_rows.txt), so
+        it is computed as "full_then_select" and the cost is monotone in the selection.  "narrow": _narrow_plan().
+        "terms": the block products, restricted to the selection if there is one (_Assembly)."""
+        if cols_host is not None and len(cols_host) >= FULL_THEN_SELECT * self.shape[1] \
+                and len(cols_host) > 0 and self._full_product_pays_cols(cols_host):
+            return "full_then_select", None
+        parts = self._parts()
+        if parts is not None:
+            return "parts", parts
+        if cols_host is not None and plan is None and NARROW_COLS > 0:
+            nar = self._for_cols("_narrow_cache", cols_host, lambda: self._narrow_plan(cols_host))
+            if nar == "wide":
+                return "wide", None
+            if nar is not None and d.dtype == D.torch_dtype(self.dtype):
+                return "narrow", nar
+        return "terms", None
+
+    def _full_then_select(self, d, rows, cols_host, plan, colsum, center, xtv):
+        """The unrestricted product, then its rows and columns `cols_host` (the column sums: each block's subset)."""
+        cs_full = [None] * len(self.matrices) if colsum is not None else None
+        full = self._sandwich_dev(d, rows, None, None, cs_full, center=center, xtv=xtv)
+        if colsum is not None:
+            sub_d = (plan if plan is not None else self._sandwich_plan(cols_host))[1]
+            for i, c in enumerate(cs_full):
+                if c is not None:
+                    colsum[i] = _take(c, sub_d[i])
+        cd = self._cols_dev64(cols_host)
+        return full.index_select(0, cd).index_select(1, cd)
+
     def _sandwich_dev(self, d, rows, cols_host, plan=None, colsum=None, center=None, xtv=None):
         """d: device tensor; rows: int32 device tensor or None; cols_host: host list or None.
         Returns the float64 (n_cols, n_cols) device result (split_matrix.py:324-356).
+        plan: the result of _sandwich_plan(cols_host), staged by the caller (sandwich_graph: no upload in here).
         colsum: optional list (one slot per block) that receives X_block' d[rows] (restricted to
         the block's columns) wherever it falls out of the sandwich for free.
         center (_Centering or None): dense blocks whose SELF term is computed centred (the cross terms stay
         raw); it also records which column sums are centred.
         xtv (_Xtv or None): collects X_b' v of the blocks whose self-term kernel can carry a second vector (only
         on the unrestricted-column paths; the row-part and narrow-selection paths leave it empty)."""
-        if cols_host is not None and len(cols_host) >= FULL_THEN_SELECT * self.shape[1] \
-                and len(cols_host) > 0 and self._full_product_pays_cols(cols_host):
-            pos_d, sub_d, n_cols = plan if plan is not None else self._sandwich_plan(cols_host)
-            cs_full = [None] * len(self.matrices) if colsum is not None else None
-            full = self._sandwich_dev(d, rows, None, None, cs_full, center=center, xtv=xtv)
-            if colsum is not None:
-                for i, c in enumerate(cs_full):
-                    if c is not None:
-                        colsum[i] = c if sub_d[i] is None else c[sub_d[i].to(torch.int64)]
-            cd = self._cols_dev64(cols_host)
-            return full.index_select(0, cd).index_select(1, cd)
-        parts = self._parts()
-        if parts is not None:
-            return self._sandwich_parts(parts, d, rows, cols_host, colsum, center)
-        if cols_host is not None and plan is None and NARROW_COLS > 0:
-            nar = self._narrow_plan(cols_host)
-            if nar == "wide":
-                # more selected dense + sparse columns than the dense-block form takes: the generic
-                # restricted kernels stream everything and cost the full product or more (3.35-3.7
-                # vs 3.5 ms at 2M rows, profiles/r3_cols_rows.txt) -- the tuned unrestricted
-                # product + selection is never slower, so the cost is monotone in the selection
-                cs_full = [None] * len(self.matrices) if colsum is not None else None
-                full = self._sandwich_dev(d, rows, None, None, cs_full, center=center, xtv=xtv)
-                if colsum is not None:
-                    _, sub_sel, _ = self._sandwich_plan(cols_host)
-                    for i, c in enumerate(cs_full):
-                        if c is not None:
-                            colsum[i] = c if sub_sel[i] is None else c[sub_sel[i].to(torch.int64)]
-                cd = self._cols_dev64(cols_host)
-                return full.index_select(0, cd).index_select(1, cd)
-            if nar is not None and d.dtype == D.torch_dtype(self.dtype):
-                return self._sandwich_narrow(nar, d, rows, colsum, center)
+        route, how = self._sandwich_route(d, cols_host, plan)
+        if route in ("full_then_select", "wide"):
+            return self._full_then_select(d, rows, cols_host, plan, colsum, center, xtv)
+        if route == "parts":
+            return self._sandwich_parts(how, d, rows, cols_host, colsum, center)
+        if route == "narrow":
+            return self._sandwich_narrow(how, d, rows, colsum, center)
         pos_d, sub_d, n_cols = plan if plan is not None else self._sandwich_plan(cols_host)
         out = D.zeros((n_cols, n_cols), torch.float64)
-        mats = self.matrices
-        empty = [sd is not None and D.nlen(sd) == 0 for sd in sub_d]
-        done = set()
-        return self._sandwich_terms(d, rows, cols_host, colsum, out, pos_d, sub_d, empty, done, center,
-                                    xtv if cols_host is None else None)
+        return _Assembly(self, d, rows, cols_host, out, pos_d, sub_d, colsum, center,
+                         xtv if cols_host is None else None).run()
 
-    def _sandwich_terms(self, d, rows, cols_host, colsum, out, pos_d, sub_d, empty, done, center=None, xtv=None):
-        """The block products of one sandwich, in line on the current stream."""
-        from .ext import dense as xd
-
-        mats = self.matrices
-        # ---- fused categorical cross terms: one pass over the dense / sparse block serves
-        #      every categorical block (tm_multi_cat_*), instead of one pass per pair
-        cat_ids = [i for i, m in enumerate(mats) if isinstance(m, CategoricalMatrix) and not empty[i]
-                   and m.shape[1] > 0]
-        budget = (128 * 1024) // 8       # LDS tiles are made of doubles for float32 data too
-        groups = self._cat_groups(cat_ids)
-        if groups:
-            d_eff = D.masked_d(d, rows)   # row restriction = masked d (excluded rows contribute 0)
-        for grp in groups:
-            cats = [(mats[i]._dev(), mats[i].shape[1], mats[i].drop_first) for i in grp]
-            total = sum(c[1] for c in cats)
-            offs = np.concatenate([[0], np.cumsum([c[1] for c in cats])])
-            for w, mw in enumerate(mats):
-                if empty[w] or mw.dtype != self.dtype or d.dtype != D.torch_dtype(self.dtype):
-                    continue
-                stacked = self._fused_cats(mw, cats, grp, d_eff, rows, total, budget, d)
-                if stacked is None:
-                    continue
-                # no column restriction: the stacked result goes out in ONE scatter (24
-                # categoricals x 2 operands were 48 launches of ~5 us)
-                whole = cols_host is None and len(grp) > 1
-                if whole:
-                    cache = self.__dict__.setdefault("_group_pos", {})
-                    gpos = cache.get(tuple(grp))
-                    if gpos is None:
-                        gpos = cache[tuple(grp)] = torch.cat([pos_d[i] for i in grp])
-                    xsplit.scatter_block(stacked.contiguous(), gpos, pos_d[w], out, mirror=True)
-                for ci, i in enumerate(grp):
-                    res = stacked[int(offs[ci]):int(offs[ci + 1])]
-                    if (colsum is not None and colsum[w] is None and not mats[i].drop_first
-                            and not mats[i]._has_missings):
-                        cs = res.sum(dim=0)           # all levels of a complete categorical
-                        colsum[w] = cs if sub_d[w] is None else cs[sub_d[w].to(torch.int64)]
-                    if not whole:
-                        res = CategoricalMatrix._restrict(res, sub_d[i], sub_d[w])
-                        xsplit.scatter_block(res.contiguous(), pos_d[i], pos_d[w], out, mirror=True)
-                    done.add((min(i, w), max(i, w)))
-        # ---- categoricals with too many levels for the fused groups, against a NARROW dense block: the generic
-        #      LDS-tile kernel holds [all their levels][8 columns or fewer] at once, so one pass over the block
-        #      serves them all (the reference's design dense_cat: two 1000-level categoricals x 5 dense columns were
-        #      two passes of 0.08 ms)
-        big = [i for i in cat_ids if mats[i].shape[1] > self.FUSED_LEVELS]
-        if len(big) >= 2 and len(big) <= 16 and d.dtype == D.torch_dtype(self.dtype):
-            cats = [(mats[i]._dev(), mats[i].shape[1], mats[i].drop_first) for i in big]
-            offs = np.concatenate([[0], np.cumsum([c[1] for c in cats])])
-            d_big = None
-            for w, mw in enumerate(mats):
-                if (empty[w] or not isinstance(mw, DenseMatrix) or mw.dtype != self.dtype
-                        or not xsplit.multi_cat_dense_tile_ok(cats, mw._dev_c())):
-                    continue
-                if d_big is None:
-                    d_big = D.masked_d(d, rows)
-                stacked = xsplit.multi_cat_dense_sandwich(cats, d_big, mw._dev_c())
-                for ci, i in enumerate(big):
-                    res = stacked[int(offs[ci]):int(offs[ci + 1])]
-                    if (colsum is not None and colsum[w] is None and not mats[i].drop_first
-                            and not mats[i]._has_missings):
-                        cs = res.sum(dim=0)
-                        colsum[w] = cs if sub_d[w] is None else cs[sub_d[w].to(torch.int64)]
-                    res = CategoricalMatrix._restrict(res, sub_d[i], sub_d[w])
-                    xsplit.scatter_block(res.contiguous(), pos_d[i], pos_d[w], out, mirror=True)
-                    done.add((min(i, w), max(i, w)))
-        # ---- all categorical x categorical tables that fit an LDS tile, and the categorical
-        #      diagonals, in ONE pass over the codes (tm_multi_cat_pairs_*): a design with k
-        #      categoricals has k (k - 1) / 2 of them, one launch each was ~30 us apiece
-        cat_diag = {}
-        diag_scattered = set()
-        # TABMAT_AMD_DETERMINISTIC: the diagonals must come from the fixed-order histogram
-        # (csrc/cat_det.hip), not from LDS-atomic tables -- no fused plan, no row-sum shortcut
-        det = _cm.DETERMINISTIC
-        plan = self._cat_pairs_plan() if CAT_PAIRS_FUSED and not det else None
-        if (plan is not None and plan.n_pairs > 0
-                and d.dtype in (torch.float32, torch.float64)
-                and d.dtype == D.torch_dtype(self.dtype)):
-            cl = [(mats[i]._dev(), mats[i].shape[1], mats[i].drop_first) for i in plan.cat_ids]
-            # column restriction: the full tables are accumulated, the scatter drops the
-            # unselected levels (position -1)
-            pos_sel = None if cols_host is None else self._pairs_pos_sel(plan, cols_host)
-            tables = xsplit.multi_cat_pairs(plan, cl, d, rows, out, pos=pos_sel)
-            for i, j, toff, li, lj, stride in plan.pairs:
-                if i == j:
-                    if not empty[i]:
-                        full = tables[toff:toff + (li - 1) * stride + 1:stride]
-                        if sub_d[i] is not None and colsum is not None:
-                            full = full[sub_d[i].to(torch.int64)]
-                        cat_diag[i] = full.to(d.dtype)
-                        diag_scattered.add(i)
-                else:
-                    done.add((i, j))
-        # the other categorical x categorical tables: the diagonal of a categorical block is the
-        # row sum of its table with any COMPLETE partner (every row has exactly one level there),
-        # which saves its histogram pass
-        complete = [isinstance(m, CategoricalMatrix) and not m.drop_first and not m._has_missings
-                    and sub_d[k] is None and not empty[k] for k, m in enumerate(mats)]
-        for i, mi in enumerate(mats):
-            if empty[i] or not isinstance(mi, CategoricalMatrix):
-                continue
-            for j in range(i + 1, len(mats)):
-                if empty[j] or not isinstance(mats[j], CategoricalMatrix) or (i, j) in done:
-                    continue
-                res = mi._cross_sandwich_dev(mats[j], d, rows, sub_d[i], sub_d[j])
-                xsplit.scatter_block(res.contiguous(), pos_d[i], pos_d[j], out, mirror=True)
-                done.add((i, j))
-                if DIAG_FROM_PAIRS and not det and complete[j] and i not in cat_diag:
-                    cat_diag[i] = res.sum(dim=1)
-                if DIAG_FROM_PAIRS and not det and complete[i] and j not in cat_diag:
-                    cat_diag[j] = res.sum(dim=0)
-        # self terms first, then the remaining cross terms
-        for i, mi in enumerate(mats):
-            if empty[i]:
-                continue
-            if isinstance(mi, CategoricalMatrix):
-                diag = cat_diag[i] if i in cat_diag else mi._sandwich_diag_dev(d, rows, sub_d[i])
-                if colsum is not None:
-                    colsum[i] = diag          # one-hot entries are 0 / 1: C' d = diag(C' D C)
-                if i not in diag_scattered:
-                    xsplit.scatter_block(diag, pos_d[i], pos_d[i], out, diag=True)
-            elif (xtv is not None and colsum is None and center is None and isinstance(mi, DenseMatrix)
-                  and sub_d[i] is None and (both := mi._sandwich_xtv_dev(d, xtv.v, rows)) is not None):
-                # X_dense' v comes out of the syrk's own pass (sandwich_and_transpose_matvec)
-                res, xtv.out[i] = both
-                xsplit.scatter_block(res, pos_d[i], pos_d[i], out)
-            elif (colsum is not None and colsum[i] is None and isinstance(mi, DenseMatrix)
-                  and rows is None and sub_d[i] is None
-                  and (both := mi._sandwich_xtd_dev(d, cen_i := (center.get(i) if center else None))) is not None):
-                # X_dense' d comes out of the syrk's own pass (csrc/syrk_i8.hip, csrc/syrk_co.hip)
-                res, colsum[i] = both
-                if cen_i is not None:
-                    center.cs_centered.add(i)
-                xsplit.scatter_block(res, pos_d[i], pos_d[i], out)
-            elif isinstance(mi, DenseMatrix) and center is not None and center.get(i) is not None:
-                res = mi._sandwich_dev(d, rows, sub_d[i], center=center.get(i))
-                xsplit.scatter_block(res, pos_d[i], pos_d[i], out)
-            else:
-                res = mi._sandwich_dev(d, rows, sub_d[i])
-                xsplit.scatter_block(res, pos_d[i], pos_d[i], out)
-        for i, mi in enumerate(mats):
-            if empty[i]:
-                continue
-            for j in range(i + 1, len(mats)):
-                if empty[j] or (i, j) in done:
-                    continue
-                # sparse x dense: X_sparse' d rides along in the gather's stream loop
-                si, di = (i, j) if isinstance(mi, SparseMatrix) else (j, i)
-                if (colsum is not None and colsum[si] is None and isinstance(mats[si], SparseMatrix)
-                        and isinstance(mats[di], DenseMatrix)):
-                    box = []
-                    res = mats[si]._cross_sandwich_dev(mats[di], d, rows, sub_d[si], sub_d[di],
-                                                       colsum_box=box)
-                    if box:
-                        colsum[si] = box[0]
-                    if si != i:
-                        res = res.T
-                else:
-                    res = mi._cross_sandwich_dev(mats[j], d, rows, sub_d[i], sub_d[j])
-                xsplit.scatter_block(res.contiguous(), pos_d[i], pos_d[j], out, mirror=True)
-        return out
+    def _like(self, res, v, on_dev):
+        """The device result `res` of a product with v on v's side: as it is, or as numpy in the result dtype."""
+        if on_dev:
+            return res
+        res = D.to_host(res)
+        if np.issubdtype(v.dtype, np.floating):
+            res = res.astype(np.result_type(self.dtype, v.dtype), copy=False)
+        return res
 
     def sandwich_graph(self, d, rows=None, cols=None):
         """HIP-graph form of `sandwich` for solvers that call it with the same `rows` / `cols`
@@ -1012,11 +1055,7 @@ class SplitMatrix(MatrixBase):
             acc = _Xtv(v_dev)
         H = self._sandwich_dev(D.to_dev(d), D.idx_dev(rows_n), cols_n, xtv=acc)
         g, _ = self._transpose_matvec_dev(v_dev, rows_n, cols_n, done=None if acc is None else acc.out)
-        if not v_dev_side:
-            g = D.to_host(g)
-            if np.issubdtype(v.dtype, np.floating):
-                g = g.astype(np.result_type(self.dtype, v.dtype), copy=False)
-        return (H if d_dev_side else D.to_host(H)), g
+        return (H if d_dev_side else D.to_host(H)), self._like(g, v, v_dev_side)
 
     def sandwich_matvec(self, d, u, rows=None, cols=None):
         """sandwich(d, rows, cols) @ u without forming the (k, k) sandwich (MatrixBase.sandwich_matvec), result
@@ -1053,17 +1092,10 @@ class SplitMatrix(MatrixBase):
         kernel.  d: device vector over all rows; rows: int32 device tensor or None.  Row parts are summed."""
         p = self.shape[1]
         parts = self._parts()
+        s2 = D.zeros((p,), torch.float64)
+        s1 = D.zeros((p,), torch.float64) if want_s1 else None
         if parts is not None:
-            s2 = D.zeros((p,), torch.float64)
-            s1 = D.zeros((p,), torch.float64) if want_s1 else None
-            for a, b, part in parts:
-                r = None
-                if rows is not None:
-                    r64 = rows.to(torch.int64)
-                    sel = r64[(r64 >= a) & (r64 < b)]
-                    if sel.numel() == 0:
-                        continue
-                    r = (sel - a).to(torch.int32)
+            for a, b, part, r in _row_parts(parts, rows):
                 p2, p1 = part._sdiag_dev(d[a:b], r, cols_host, centers, want_s1)
                 s2 += p2
                 if want_s1:
@@ -1073,8 +1105,6 @@ class SplitMatrix(MatrixBase):
         if cols_host is not None:
             mask = np.zeros(p, dtype=bool)
             mask[np.asarray(cols_host, dtype=np.int64)] = True
-        s2 = D.zeros((p,), torch.float64)
-        s1 = D.zeros((p,), torch.float64) if want_s1 else None
         idx_d = self._full_dev_indices()
         for b, (mb, idx) in enumerate(zip(self.matrices, self.indices)):
             if mb.shape[0] == 0 or (mask is not None and not mask[idx].any()):
@@ -1116,38 +1146,33 @@ class SplitMatrix(MatrixBase):
         v_dev = D.to_dev(v, tdt)
         if cols_n is not None and len(cols_n) >= FULL_THEN_SELECT_MV * self.shape[1] and len(cols_n) > 0 \
                 and self._blocks_finite():      # (0 x inf of an excluded column would leak a NaN)
-            cd = self._cols_dev64(cols_n)           # X[:, cols] v[cols] = X (v with zeros elsewhere)
-            vm = torch.zeros_like(v_dev)
-            vm[cd] = v_dev[cd]
-            v_dev, cols_n = vm, None
-        if v_dev.ndim == 1:
-            res = self._matvec1_dev(v_dev, cols_n)
-        else:
-            # 2-D operand (no categorical block here): one multi-right-hand-side launch per block
-            from .ext import dense as xd
-            from .ext import sparse as xs
-
-            _, sub_d, _ = self._sandwich_plan(cols_n)
-            idx_d = self._full_dev_indices()
-            res = D.zeros((self.shape[0], v_dev.shape[1]), tdt)
-            for mat, idx, scd in zip(self.matrices, idx_d, sub_d):
-                if scd is not None and D.nlen(scd) == 0:
-                    continue
-                if scd is not None and D.nlen(scd) == mat.shape[1]:
-                    scd = None
-                vb = v_dev[idx]
-                if isinstance(mat, DenseMatrix):
-                    res += xd.dense_matvec_multi(mat._dev(), vb, None, scd, False)
-                else:
-                    res += xs.csr_matvec_multi(mat._dev(), vb, None, scd, False)
-        if not on_dev:
-            res = D.to_host(res)
-            if np.issubdtype(v.dtype, np.floating):
-                res = res.astype(np.result_type(self.dtype, v.dtype), copy=False)
+            # X[:, cols] v[cols] = X (v with zeros elsewhere)
+            v_dev, cols_n = _zeros_outside(v_dev, self._cols_dev64(cols_n)), None
+        res = self._matvec1_dev(v_dev, cols_n) if v_dev.ndim == 1 else self._multi_rhs_dev(v_dev, None, cols_n, False)
+        res = self._like(res, v, on_dev)
         if out is None:
             return res
         out += res
         return out
+
+    def _multi_rhs_dev(self, v_dev, rd, cols_n, transpose, no_rows=False):
+        """X[:, cols] v or X[rows, cols]' v of a 2-D operand (no categorical block here): one launch per block."""
+        from .ext import dense as xd
+        from .ext import sparse as xs
+
+        pos_d, sub_d, n_cols = self._sandwich_plan(cols_n)
+        res = D.zeros((n_cols if transpose else self.shape[0], v_dev.shape[1]), v_dev.dtype)
+        for mat, idx, pd, scd in zip(self.matrices, self._full_dev_indices(), pos_d, sub_d):
+            if no_rows or (scd is not None and D.nlen(scd) == 0):
+                continue
+            if scd is not None and D.nlen(scd) == mat.shape[1]:
+                scd = None
+            product = xd.dense_matvec_multi if isinstance(mat, DenseMatrix) else xs.csr_matvec_multi
+            if transpose:
+                res[pd] += product(mat._dev(), v_dev, rd, scd, True)
+            else:
+                res += product(mat._dev(), v_dev[idx], None, scd, False)
+        return res
 
     def _matvec1_dev(self, v_dev, cols_n, skip=()):
         """X[:, cols] v[cols] of a 1-D device v (full length p, the matrix dtype) as a new device vector; the
@@ -1161,14 +1186,8 @@ class SplitMatrix(MatrixBase):
             # all categorical blocks in ONE pass (one gather + one launch per block before:
             # 20 categoricals 0.33 ms for 0.18 GB); a column selection becomes zeros in the
             # coefficient vector these blocks read
-            cl = [(self.matrices[i]._dev(), self.matrices[i].shape[1], self.matrices[i].drop_first)
-                  for i in plan.cat_ids]
-            vm = v_dev
-            if cols_n is not None:
-                cd = self._cols_dev64(cols_n)
-                vm = torch.zeros_like(v_dev)
-                vm[cd] = v_dev[cd]
-            xsplit.multi_cat_matvec(plan, cl, vm, res)
+            vm = v_dev if cols_n is None else _zeros_outside(v_dev, self._cols_dev64(cols_n))
+            xsplit.multi_cat_matvec(plan, self._cat_args(plan.cat_ids), vm, res)
             fused = set(plan.cat_ids)
         for bi, (mat, idx, scd) in enumerate(zip(self.matrices, idx_d, sub_d)):
             if (scd is not None and D.nlen(scd) == 0) or bi in fused or bi in skip:
@@ -1192,6 +1211,12 @@ class SplitMatrix(MatrixBase):
                 best = bi
         return best
 
+    def _fused_dense_pass(self, bi, u_full):
+        """For the fused dense block bi: (its kernel operand, its positions, its part of u_full, the OTHER blocks' X u)."""
+        idx = self._full_dev_indices()[bi]
+        return (self.matrices[bi]._smv_block(), idx, u_full[idx].contiguous(),
+                self._matvec1_dev(u_full, None, skip=(bi,)))
+
     def _smv_dev(self, dm, u_full, shift=None, centers=None):
         """(g, w) with t = X u_full + shift, w = dm * t, g = X' w over ALL columns (device, the matrix dtype), or
         None when no dense block takes the fused pass.  The other blocks' X_b u_b (t_o) comes first; one pass
@@ -1199,14 +1224,9 @@ class SplitMatrix(MatrixBase):
         transpose_matvec runs on w.  Returns (g, w, fix).  centers ({block: column centres} or None): D is read
         centred -- t is the same, g_D comes back as (X_D - 1 c')' w and fix = (positions of D, c): the caller adds
         c sum(w) there (fix is None otherwise).  shift: one-element device tensor or None."""
-        bi = self._smv_dense_block()
-        if bi is None or self._parts() is not None:
+        if (bi := self._smv_dense_block()) is None or self._parts() is not None:
             return None
-        mat = self.matrices[bi]
-        blk = mat._smv_block()
-        idx = self._full_dev_indices()[bi]
-        u_D = u_full[idx].contiguous()
-        t_o = self._matvec1_dev(u_full, None, skip=(bi,))
+        blk, idx, u_D, t_o = self._fused_dense_pass(bi, u_full)
         c, shift = _centre_and_shift(centers, bi, u_D, shift)
         g_D, w = xd_smv(blk, u_D, dm, t_add=t_o, center=c, shift=shift, want_w=True)
         g, _ = self._transpose_matvec_dev(w, None, None, done={bi: g_D})
@@ -1219,14 +1239,9 @@ class SplitMatrix(MatrixBase):
         (tm_dense_glm_loss_grad_*) then gives eta = X_D u_D + that + shift, the family's r, d and loss, and
         g_D = X_D' r; the other blocks' transpose_matvec runs on r.  family: the resolved (code, param) of _glm_args;
         centers / shift / fix as in _smv_dev."""
-        bi = self._smv_dense_block()
-        if bi is None or self._parts() is not None:
+        if (bi := self._smv_dense_block()) is None or self._parts() is not None:
             return None
-        mat = self.matrices[bi]
-        blk = mat._smv_block()
-        idx = self._full_dev_indices()[bi]
-        u_D = u_full[idx].contiguous()
-        t_o = self._matvec1_dev(u_full, None, skip=(bi,))
+        blk, idx, u_D, t_o = self._fused_dense_pass(bi, u_full)
         if t_add is not None:
             t_o += t_add
         c, shift = _centre_and_shift(centers, bi, u_D, shift)
@@ -1273,11 +1288,9 @@ class SplitMatrix(MatrixBase):
                 # every categorical block's histogram from ONE pass over the codes (one launch per
                 # block was ~35 us each: 20 categoricals 0.69 ms for 0.18 GB); a column selection
                 # picks its entries out of the full-length result
-                cl = [(self.matrices[i]._dev(), self.matrices[i].shape[1], self.matrices[i].drop_first)
-                      for i in plan.cat_ids]
                 direct = cols_n is None and tdt == torch.float64
                 tgt = res if direct else D.zeros((self.shape[1],), torch.float64)
-                xsplit.multi_cat_pairs(plan, cl, v_dev, rd, tgt, vector=True)
+                xsplit.multi_cat_pairs(plan, self._cat_args(plan.cat_ids), v_dev, rd, tgt, vector=True)
                 if not direct:
                     if cols_n is not None:
                         tgt = tgt[self._cols_dev64(cols_n)]
@@ -1291,27 +1304,14 @@ class SplitMatrix(MatrixBase):
                 elif isinstance(mat, CategoricalMatrix):
                     full = D.zeros((mat.shape[1],), tdt)
                     mat._transpose_matvec_dev(v_dev, rd, scd, full)
-                    part = full if scd is None else full[scd.to(torch.int64)]
+                    part = _take(full, scd)
                 else:
                     if scd is not None and D.nlen(scd) == mat.shape[1]:
                         scd = None  # sorted unique columns covering the block = all of them
                     part = mat._matvec_dev(v_dev, rd, scd, None, True)
                 res[pd] += part
         else:
-            from .ext import dense as xd
-            from .ext import sparse as xs
-
-            res = D.zeros((n_cols, v_dev.shape[1]), tdt)
-            empty_rows = rows_n is not None and len(rows_n) == 0
-            for mat, pd, scd in zip(self.matrices, pos_d, sub_d):
-                if empty_rows or (scd is not None and D.nlen(scd) == 0):
-                    continue
-                if scd is not None and D.nlen(scd) == mat.shape[1]:
-                    scd = None
-                if isinstance(mat, DenseMatrix):
-                    res[pd] += xd.dense_matvec_multi(mat._dev(), v_dev, rd, scd, True)
-                else:
-                    res[pd] += xs.csr_matvec_multi(mat._dev(), v_dev, rd, scd, True)
+            res = self._multi_rhs_dev(v_dev, rd, cols_n, True, rows_n is not None and len(rows_n) == 0)
         if select is not None:
             res, cols_n = res[self._cols_dev64(select)], select
         return res, cols_n
@@ -1329,10 +1329,7 @@ class SplitMatrix(MatrixBase):
         rows_n = normalize_index(rows, self.shape[0])
         cols_n = collapse_identity(normalize_index(cols, self.shape[1]), self.shape[1])
         res, cols_n = self._transpose_matvec_dev(v, rows_n, cols_n)
-        if not on_dev:
-            res = D.to_host(res)
-            if np.issubdtype(v.dtype, np.floating):
-                res = res.astype(np.result_type(self.dtype, v.dtype), copy=False)
+        res = self._like(res, v, on_dev)
         if out is None:
             return res
         if cols_n is None:
