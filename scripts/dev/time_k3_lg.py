@@ -21,7 +21,7 @@ def timed(fn, reps=4):
 ell = sm._ell(wide=True)
 t0, ref = timed(lambda: xs.csr_dense_sandwich_ell(ell, Bd, d))
 print(f"ellw: {t0:.3f} ms  slots {ell.vals.numel()/sm._dev().data.numel():.2f}x nnz", flush=True)
-del ell; sm._ellwblk = None
+del ell; sm.__dict__.pop("_ellw_twin", None)
 lg = sm._lg()
 print(f"lg twin: round0 slots {lg.vals.numel()/sm._dev().data.numel():.2f}x nnz, extra rounds {lg.xptr[-1].item()} "
       f"of {lg.xptr.numel()-1} blocks, unc {lg.unc}", flush=True)

@@ -99,6 +99,11 @@ def nlen(t: Optional[torch.Tensor]) -> int:
     return 0 if t is None else int(t.numel())
 
 
+def free_bytes(device=None) -> int:
+    """Free HBM on `device` (None: the current one) -- the one probe the host cost models read."""
+    return torch.cuda.mem_get_info(device)[0]
+
+
 def masked_d(d: torch.Tensor, rows: Optional[torch.Tensor], as_set: bool = False) -> torch.Tensor:
     """A row restriction as a masked weight vector for the kernels that make one full pass: rows outside
     `rows` get d = 0.  What a REPEATED row id means follows the reference product by product, and every

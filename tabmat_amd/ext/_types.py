@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import os
+import weakref
 from dataclasses import dataclass
 
 import numpy as np
@@ -74,6 +75,16 @@ class CsrDev:
         self.indptr = indptr
         self.n = int(n)
         self.m = int(m)
+        self._cm = self._cm_rec = self._cm_rec_pk = self._cscb = self._row_tab = self._pb = None     # see _twin
+
+    def _twin(self, name, build, valid=None):
+        """The twin cached under `name` (None: not built): build() the first time, after a reset to None, and when
+        valid(twin) says that the cached one no longer serves."""
+        hit = getattr(self, name)
+        if hit is None or (valid is not None and not valid(hit)):
+            hit = build()
+            setattr(self, name, hit)
+        return hit
 
     @property
     def dtype(self):
@@ -84,8 +95,6 @@ class CsrDev:
         """int32 column indices (widened from the 16-bit twin into the shared scratch once compacted)."""
         if self._ind32 is not None:
             return self._ind32
-        import weakref
-
         _WIDE[:] = [(o, t) for o, t in _WIDE if o() is not None]      # (scratch of blocks that are gone)
         for k, (owner, t) in enumerate(_WIDE):
             if owner() is self:
@@ -118,22 +127,20 @@ class CsrDev:
         return False
 
     def nbytes(self) -> int:
-        """HBM bytes of the CSR arrays and of every twin built so far."""
-        seen, tot = set(), 0
+        """HBM bytes of the CSR arrays and of every twin built so far (as ever without the block list `_pb` and the
+        row table's ranges: bench.py reports this number as resident_bytes)."""
+        seen = {}
 
         def add(t):
-            nonlocal tot
             if isinstance(t, torch.Tensor):
-                if t.data_ptr() not in seen:
-                    seen.add(t.data_ptr())
-                    tot += t.numel() * t.element_size()
+                seen.setdefault(t.data_ptr(), t.numel() * t.element_size())
             elif isinstance(t, (tuple, list)):
                 for x in t:
                     add(x)
 
-        for v in self.__dict__.values():
-            add(v)
-        return tot
+        add((self.data, self._ind32, self._ind16, self.indptr, self._cm, self._cm_rec, self._cm_rec_pk, self._cscb,
+             self._row_tab))
+        return sum(seen.values())
 
     def chunk_col8(self):
         """uint8 [nnz]: the column of every chunk-major entry inside its column chunk (tm_sparse_sandwich_blocks_u8_*,
@@ -157,8 +164,7 @@ class CsrDev:
         """(cm_data, cm_col8 uint8, cptr int32 [NCH, n + 1]): the entries regrouped by column chunk,
         inside a chunk by row (see tm_sparse_sandwich_chunked_*); cm_col8 = the column INSIDE the chunk.
         Built once per block (ingest: one device key sort), cached."""
-        cm = getattr(self, "_cm", None)
-        if cm is None:
+        def build():
             from .._lib import lib
 
             ch = int(lib().tm_sparse_chunk_cols())
@@ -188,79 +194,50 @@ class CsrDev:
             start = (torch.cumsum(per, dim=0) - per).view(nch, self.n)
             ends = torch.cat([start[1:, 0], torch.tensor([nnz], device=dev, dtype=torch.int64)])
             cptr = torch.cat([start, ends[:, None]], dim=1).to(torch.int32).contiguous()
-            cm = (cm_data, cm_col8, cptr)
-            self._cm = cm
-        return cm
+            return cm_data, cm_col8, cptr
+
+        return self._twin("_cm", build)
+
+    def _chunk_records(self, packed: bool):
+        """The record stream of the chunk-major twin, one record per entry: the value (f64: two words), then {column,
+        row} (16 bytes in all; f32: a zero word at the end) or, packed, the one word row << 7 | column inside the
+        chunk.  Flat int32 with 4 words of tail padding (the kernels' clamped look-ahead may name entry nnz); the rows
+        come from the chunk pointers (inside a chunk the entries are in row order).  Filled column by column: a 2-D
+        gather of more than 2^32 bytes came back scrambled on this stack."""
+        cm_data, cm_c8, cptr = self.chunk_major()
+        nnz = int(cm_data.numel())
+        V = 2 if cm_data.dtype == torch.float64 else 1              # words of a value
+        W = V + 1 if packed else 4
+        buf = torch.zeros(nnz * W + 4, dtype=torch.int32, device=cptr.device)
+        rec = buf[:nnz * W].view(nnz, W)
+        words = cm_data.view(torch.int32).view(nnz, V)
+        for k in range(V):
+            rec[:, k] = words[:, k]
+        if not packed:
+            rec[:, V] = self.chunk_cols32()
+        ar = torch.arange(self.n, device=cptr.device, dtype=torch.int64 if packed else torch.int32)
+        pos = 0
+        for c in range(int(cptr.shape[0])):
+            k = int(cptr[c, -1].item()) - int(cptr[c, 0].item())
+            if k:
+                cnt = (cptr[c, 1:] - cptr[c, :-1]).to(torch.int64)
+                rows = torch.repeat_interleave(ar, cnt, output_size=k)
+                if packed:
+                    word = (rows << 7) | cm_c8[pos:pos + k].to(torch.int64)
+                    rows = torch.where(word >= 2**31, word - 2**32, word).to(torch.int32)
+                rec[pos:pos + k, V if packed else V + 1] = rows
+            pos += k
+        return buf if packed else rec
 
     def chunk_records(self):
-        """cm_rec int32 [nnz, 4]: one 16-byte record {value, column, row} per entry of the chunk-major twin
-        (f64: value as two words; f32: {value bits, column, row, 0}) for tm_sparse_sandwich_pairs_*.  Built on first
-        use (the rows from the chunk pointers: inside a chunk the entries are in row order), cached.  (Filled
-        column by column: a 2-D gather of more than 2^32 bytes came back scrambled on this stack.)"""
-        cr = getattr(self, "_cm_rec", None)
-        if cr is None:
-            cm_data, _, cptr = self.chunk_major()
-            cm_ind = self.chunk_cols32()
-            dev = cptr.device
-            nnz = int(cm_data.numel())
-            ar = torch.arange(self.n, device=dev, dtype=torch.int32)
-            # (one record of tail padding, as the packed form has: the kernel's clamped look-ahead may name entry nnz)
-            cr = torch.zeros((nnz + 1, 4), dtype=torch.int32, device=dev)[:nnz]
-            f64 = cm_data.dtype == torch.float64
-            if f64:
-                words = cm_data.view(torch.int32).view(nnz, 2)
-                cr[:, 0] = words[:, 0]
-                cr[:, 1] = words[:, 1]
-                cr[:, 2] = cm_ind
-            else:
-                cr[:, 0] = cm_data.view(torch.int32)
-                cr[:, 1] = cm_ind
-            pos = 0
-            for c in range(int(cptr.shape[0])):
-                k = int(cptr[c, -1].item()) - int(cptr[c, 0].item())
-                if k:
-                    cnt = (cptr[c, 1:] - cptr[c, :-1]).to(torch.int64)
-                    cr[pos:pos + k, 3 if f64 else 2] = torch.repeat_interleave(ar, cnt, output_size=k)
-                pos += k
-            self._cm_rec = cr
-        return cr
+        """cm_rec int32 [nnz, 4]: 16-byte records {value, column, row} (f32: {value bits, column, row, 0}) for
+        tm_sparse_sandwich_pairs_*.  Built on first use, cached."""
+        return self._twin("_cm_rec", lambda: self._chunk_records(False))
 
     def chunk_records_packed(self):
         """int32 [nnz * W + 4] (W = 3 for f64, 2 for f32): packed records {value, row << 7 | column inside the chunk}
         for tm_sparse_sandwich_pairs_pk_* (n < 2^25), or None."""
-        cr = getattr(self, "_cm_rec_pk", False)
-        if cr is False:
-            cr = None
-            if self.n < 2**25:
-                from .._lib import lib
-
-                ch = int(lib().tm_sparse_chunk_cols())
-                cm_data, cm_c8, cptr = self.chunk_major()
-                dev = cptr.device
-                nnz = int(cm_data.numel())
-                f64 = cm_data.dtype == torch.float64
-                W = 3 if f64 else 2
-                buf = torch.zeros(nnz * W + 4, dtype=torch.int32, device=dev)
-                rec = buf[:nnz * W].view(nnz, W)
-                if f64:
-                    words = cm_data.view(torch.int32).view(nnz, 2)
-                    rec[:, 0] = words[:, 0]
-                    rec[:, 1] = words[:, 1]
-                else:
-                    rec[:, 0] = cm_data.view(torch.int32)
-                ar = torch.arange(self.n, device=dev, dtype=torch.int64)
-                pos = 0
-                for c in range(int(cptr.shape[0])):
-                    k = int(cptr[c, -1].item()) - int(cptr[c, 0].item())
-                    if k:
-                        cnt = (cptr[c, 1:] - cptr[c, :-1]).to(torch.int64)
-                        rows = torch.repeat_interleave(ar, cnt, output_size=k)
-                        word = (rows << 7) | cm_c8[pos:pos + k].to(torch.int64)
-                        rec[pos:pos + k, W - 1] = torch.where(word >= 2**31, word - 2**32, word).to(torch.int32)
-                    pos += k
-                cr = buf
-            self._cm_rec_pk = cr
-        return cr
+        return self._twin("_cm_rec_pk", lambda: self._chunk_records(True)) if self.n < 2**25 else None
 
     def pair_blocks(self, n_wg: int = 0, nw: int = 16, cyclic=None, d12=None):
         """(blocks int32 [B, 4] -- or [B, 3]: 12-byte descriptors, see K2B_DESC12 --, wg_tab int32 [W, 8], max_nb): the static block list of
@@ -274,9 +251,7 @@ class CsrDev:
         wg_tab row: {part, slot, first block, end, end of the FULL blocks, waves on the FULL list,
         first row, last row}.  Depends on the sparsity pattern only: built once, cached."""
         d12 = bool((K2B_DESC12 if d12 is None else d12) and self.n < 2**24)   # 12-byte descriptors: 24 bits of row
-        cache = self.__dict__.get("_pb")
-        if not isinstance(cache, dict):                      # (tests reset the cache with `_pb = None`)
-            cache = self.__dict__["_pb"] = {}
+        cache = self._twin("_pb", dict)                      # (tests reset the cache with `_pb = None`)
         pb = cache.get(d12)
         if pb is None:
             _, _, cptr = self.chunk_major()
@@ -429,8 +404,7 @@ class CsrDev:
         """(rows int32, vals, bstart int64, n_blocks, col_bptr int64): the CSC form of the block with
         every column's entries cut into blocks of at most tm_cat_det_block_rows() -- the input of
         tm_csc_dense_sandwich_sorted_*.  Built once (a stable device sort by column), cached."""
-        cb = getattr(self, "_cscb", None)
-        if cb is None:
+        def build():
             from .._lib import lib
 
             blk = int(lib().tm_cat_det_block_rows())
@@ -451,10 +425,31 @@ class CsrDev:
             bstart = torch.empty(n_blocks + 1, dtype=torch.int64, device=dev)
             bstart[:-1] = seg0[col_of_blk] + within * blk
             bstart[-1] = nnz
-            cb = (rows[order].contiguous(), self.data[order].contiguous(), bstart.contiguous(),
-                  n_blocks, col_bptr.contiguous())
-            self._cscb = cb
-        return cb
+            return (rows[order].contiguous(), self.data[order].contiguous(), bstart.contiguous(),
+                    n_blocks, col_bptr.contiguous())
+
+        return self._twin("_cscb", build)
+
+    def row_ranges(self, rows, as_set: bool):
+        """(rows ascending int64, ranges int32 [n_chunks, n_sel, 2]): {start, end} of every selected row in every
+        column chunk of the chunk-major twin; as_set: a repeated row once.  Kept for the LAST row list: it depends on
+        `rows` only, and the self sandwich and the cross term of one call share it (keyed on the tensor AND its
+        version counter: a caller that refills a static index buffer in place must not get the ranges of the old
+        contents)."""
+        stamp = (rows.data_ptr(), rows._version, int(rows.numel()))
+
+        def build():
+            r64 = torch.sort(rows.to(torch.int64)).values
+            dup = bool((r64[1:] == r64[:-1]).any().item()) if r64.numel() > 1 else False
+            return weakref.ref(rows), r64, dup, {}, stamp
+
+        _, r64, dup, tabs, _ = self._twin("_row_tab", build, lambda hit: hit[0]() is rows and hit[4] == stamp)
+        key = bool(as_set and dup)
+        if key not in tabs:
+            cptr = self.chunk_major()[2]
+            rr = torch.unique_consecutive(r64) if key else r64
+            tabs[key] = (rr, torch.stack([cptr[:, rr], cptr[:, rr + 1]], dim=2).contiguous())
+        return tabs[key]
 
     def take_rows(self, kind, *arg) -> "CsrDev":
         """Row-indexed copy built on the device: kind "slice" (lo, hi) or "index" (row ids)."""

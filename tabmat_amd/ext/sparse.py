@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import os
 
+import torch
 
 from .. import _device as D
 from .._lib import call
@@ -192,28 +193,8 @@ def _row_table(A: CsrDev, rows, d, as_set: bool):
     depend on the order).  as_set: a repeated row counts once -- the reference's sparse_sandwich
     turns `rows` into a mask (ext/sparse.pyx:46-48) while its csr_dense_sandwich loops over the
     list and counts a repeated row twice (ext/sparse_helpers-tmpl.cpp:67-131)."""
-    import weakref
-
-    import torch
-
-    cm_data, cm_c8, cptr = A.chunk_major()
-    # the table depends on `rows` only: the self sandwich and the cross term of one call share it
-    # (keyed on the tensor AND its version counter: a caller that refills a static index buffer in
-    # place must not get the ranges of the old contents)
-    cached = getattr(A, "_row_table", None)
-    stamp = (rows.data_ptr(), rows._version, int(rows.numel()))
-    if cached is not None and cached[0]() is rows and cached[4] == stamp:
-        _, r64, dup, tabs, _ = cached
-    else:
-        r64 = torch.sort(rows.to(torch.int64)).values
-        dup = bool((r64[1:] == r64[:-1]).any().item()) if r64.numel() > 1 else False
-        tabs = {}
-        A._row_table = (weakref.ref(rows), r64, dup, tabs, stamp)
-    key = bool(as_set and dup)
-    if key not in tabs:
-        rr = torch.unique_consecutive(r64) if key else r64
-        tabs[key] = (rr, torch.stack([cptr[:, rr], cptr[:, rr + 1]], dim=2).contiguous())
-    rr, ranges = tabs[key]
+    cm_data, cm_c8, _ = A.chunk_major()
+    rr, ranges = A.row_ranges(rows, as_set)
     return cm_data, cm_c8, ranges, rr.to(torch.int32).contiguous(), d[rr].contiguous()
 
 
@@ -268,8 +249,6 @@ def blocks_sandwich_pays(A: CsrDev) -> bool:
     """The block list is built for the regime the 8-slot chunked kernel serves (more than ~4.5
     nonzeros per row and 128-column chunk: rows regularly overflow 8 slots), when its 16 bytes per
     block fit: ~1.4 blocks per (row, tile)."""
-    import torch
-
     if not K2_BLOCKS or A.n == 0 or A.m == 0 or A.n >= 2**29:
         return False
     nnz = int(A.data.numel())
@@ -277,7 +256,7 @@ def blocks_sandwich_pays(A: CsrDev) -> bool:
     if not (0 < nnz < 2**31) or nnz / (A.n * nch) <= 4.5 or nch > 32:
         return False
     est = 16 * 2 * A.n * nch * (nch + 1) // 2          # bytes, generous
-    return est * 3 < torch.cuda.mem_get_info(A.data.device)[0] or bool(getattr(A, "_pb", None))
+    return est * 3 < D.free_bytes(A.data.device) or bool(A._pb)
 
 
 K2B_U8 = os.environ.get("TABMAT_AMD_K2B_U8", "1") == "1"     # byte columns for the block-list kernel's gathers

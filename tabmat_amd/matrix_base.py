@@ -10,6 +10,21 @@ from typing import Optional
 import numpy as np
 
 
+def _parts_with_rows(parts, rows):
+    """(a, b, part, rows rebased to the part or None) per row part, without the parts a row list leaves empty."""
+    import torch
+
+    for a, b, part in parts:
+        r = None
+        if rows is not None:
+            r64 = rows.to(torch.int64)
+            sel = r64[(r64 >= a) & (r64 < b)]
+            if sel.numel() == 0:
+                continue
+            r = (sel - a).to(torch.int32)
+        yield a, b, part, r
+
+
 class MatrixBase(ABC):
     """Base class for DenseMatrix, SparseMatrix, CategoricalMatrix and SplitMatrix."""
 
@@ -17,6 +32,16 @@ class MatrixBase(ABC):
     shape: tuple
     dtype: np.dtype
     __array_priority__ = 11  # win over ndarray in `vec @ mat` (matrix_base.py:239-241)
+
+    def _once(self, name, build, key=()):
+        """build() the first time (per `key`, e.g. a set of categorical blocks), the same value ever after -- the
+        one cache of what a block derives from its own storage: twins, cost-model verdicts, row parts.  What build()
+        returned is kept whatever it is: a None (a twin that refused the block) is not built again."""
+        cache = self.__dict__.setdefault(name, {})
+        key = tuple(key)
+        if key not in cache:
+            cache[key] = build()
+        return cache[key]
 
     @abstractmethod
     def matvec(self, other, cols=None, out=None):

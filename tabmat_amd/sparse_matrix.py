@@ -11,7 +11,7 @@ from scipy import sparse as sps
 from . import _device as D
 from .ext import sparse as xs
 from .ext._types import CsrDev, SlabCsc, SlabEll, SlabEnt, SlabLg
-from .matrix_base import MatrixBase
+from .matrix_base import MatrixBase, _parts_with_rows
 from .util import (
     check_indexer,
     check_matvec_dimensions,
@@ -30,16 +30,26 @@ ELL_MAX_PAD = 8.0
 # K3's lane-group stream (the fallback of the entry twin since round 4) in its compact form: values of the real
 # slots + a byte map, 2.7 instead of 7.7 GB at BASELINE configs[3] (False keeps the padded stream: tests only)
 LG_COMPACT = True
-# A row restriction with at most this fraction of the rows runs the row-list kernels (cost
-# proportional to len(rows)); above it the full-pass kernels with a masked d are cheaper
-# (scripts/dev/time_rows.py: break-even near one half for the self sandwich, one quarter for the
-# sparse x dense term whose row-list form pays two LDS atomics per nonzero).
 PART_NNZ = int(os.environ.get("TABMAT_AMD_PART_NNZ", str(2**31 - 2**24)))   # see split_matrix._parts
 SORTED_K3_NNZ_PER_ROW = 6.0      # below: sparse x dense on the column-sorted kernel (wide blocks)
 # largest column selection of a sparse self sandwich that is written out as a dense block (one syrk panel)
 NARROW_COLS = int(os.environ.get("TABMAT_AMD_NARROW_COLS", "128"))
+# A row restriction with at most this fraction of the rows runs the row-list kernels (cost
+# proportional to len(rows)); above it the full-pass kernels with a masked d are cheaper
+# (scripts/dev/time_rows.py: break-even near one half for the self sandwich, one quarter for the
+# sparse x dense term whose row-list form pays two LDS atomics per nonzero).
 ROW_LIST_FRACTION = 0.5
 ROW_LIST_FRACTION_K3 = 0.25
+
+
+def _select(res, L_cols, R_cols):
+    """Rows L_cols and columns R_cols of a small result (None: all of them).  Always applied, a permutation too
+    (unlike CategoricalMatrix._restrict, which skips a selection as long as the result)."""
+    if L_cols is not None:
+        res = res[L_cols.to(torch.int64)]
+    if R_cols is not None:
+        res = res[:, R_cols.to(torch.int64)]
+    return res
 
 
 class SparseMatrix(MatrixBase):
@@ -65,8 +75,6 @@ class SparseMatrix(MatrixBase):
             self._array.sum_duplicates()
         self._array_csr = None
         self._devblk = None
-        self._slabblk = None
-        self._ellblk = None
         self._shape = self._array.shape
         self._dtype = self._array.dtype
         self._init_names(column_names, term_names)
@@ -89,8 +97,6 @@ class SparseMatrix(MatrixBase):
         self._array = None
         self._array_csr = None
         self._devblk = csr
-        self._slabblk = None
-        self._ellblk = None
         self._shape = (csr.n, csr.m)
         self._dtype = np.dtype(np.float64 if csr.data.dtype == torch.float64 else np.float32)
         self.idx_dtype = np.dtype(np.int32)
@@ -123,49 +129,91 @@ class SparseMatrix(MatrixBase):
             self._devblk = CsrDev.from_scipy(self.array_csr)
         return self._devblk
 
+    def _built(self, name):
+        """What _once holds under `name`; None when it was never asked for, or was built and refused."""
+        return self.__dict__.get(name, {}).get(())
+
+    # (read by bench.py and the tests: the twin once it is built, None before that or when it was refused)
+    _entblk = property(lambda self: self._built("_ent_twin"))
+    _slabblk = property(lambda self: self._built("_slab_twin"))
+
     def _values_finite(self) -> bool:
         """True when no stored value is inf / nan (checked once).  The gather kernel implements a
         row restriction as d = 0 on the excluded rows, and inf * 0 would leak a NaN from an
         excluded row; such blocks take the generic row-list kernel instead."""
-        if getattr(self, "_finite", None) is None:
-            self._finite = bool(torch.isfinite(self._dev().data).all().item())
-        return self._finite
+        return self._once("_finite", lambda: bool(torch.isfinite(self._dev().data).all().item()))
 
     def _slab(self) -> SlabCsc:
         """Slab-blocked column-major twin used by the sparse x dense gather kernel (built on
         first use; the reference likewise materialises its CSR twin lazily)."""
-        if getattr(self, "_slabblk", None) is None:
-            self._slabblk = SlabCsc.from_csr(self._dev())
-        return self._slabblk
+        return self._once("_slab_twin", lambda: SlabCsc.from_csr(self._dev()))
 
     def _ell(self, wide: bool = False) -> SlabEll:
         """Interleaved-ELL twin used by the static sparse x dense gather kernel (C-ordered B);
-        wide: the 128-dense-column geometry used when B has more than 64 columns."""
-        name = "_ellwblk" if wide else "_ellblk"
-        if getattr(self, name, None) is None:
-            twin = SlabEll.from_csr(self._dev(), wide=wide, max_pad=ELL_MAX_PAD)
-            setattr(self, name, twin if twin is not None else False)
-        twin = getattr(self, name)
-        return twin if twin is not False else None      # None: too sparse, use the compact slab form
+        wide: the 128-dense-column geometry used when B has more than 64 columns.
+        None: too sparse, use the compact slab form."""
+        return self._once("_ellw_twin" if wide else "_ell_twin",
+                          lambda: SlabEll.from_csr(self._dev(), wide=wide, max_pad=ELL_MAX_PAD))
 
     def _lg(self) -> SlabLg:
         """Lane-group twin for the DPP-broadcast sparse x dense kernel (C-ordered B with more than
         64 columns); None when the block is too sparse or too dense for it."""
-        if getattr(self, "_lgblk", None) is None:
+        def build():
             twin = SlabLg.from_csr(self._dev(), max_pad=ELL_MAX_PAD)
-            if twin is not None and LG_COMPACT:
-                twin.compact_()
-            self._lgblk = twin if twin is not None else False
-        return self._lgblk if self._lgblk is not False else None
+            return twin.compact_() if twin is not None and LG_COMPACT else twin
+
+        return self._once("_lg_twin", build)
 
     def _ent(self) -> SlabEnt:
         """Entry twin for the run-time-indexed sparse x dense kernel (round 4, csrc/sparse_ent.hip; C-ordered B
         with more than 64 columns); None when the block is so sparse that whole batches of 16 slots per
         (slab, column group) would exceed ELL_MAX_PAD x the nonzeros, or has 2^28 rows or more."""
-        if getattr(self, "_entblk", None) is None:
-            twin = SlabEnt.from_csr(self._dev(), max_pad=ELL_MAX_PAD)
-            self._entblk = twin if twin is not None else False
-        return self._entblk if self._entblk is not False else None
+        return self._once("_ent_twin", lambda: SlabEnt.from_csr(self._dev(), max_pad=ELL_MAX_PAD))
+
+    def _ent_det(self):
+        """The entry twin for the deterministic mode: the one the products use, else (a block so sparse that the
+        padded stream exceeds ELL_MAX_PAD x its nonzeros) one built without that limit -- reproducibility was
+        asked for, the padding is its price."""
+        ent = self._ent()
+        if ent is None:
+            ent = self._once("_ent_det_twin", lambda: SlabEnt.from_csr(self._dev(), max_pad=None))
+        return ent
+
+    def _ent_for_cats(self, wide_dense: bool):
+        """The entry twin when a categorical x sparse term should run on it (SplitMatrix._fused_cats): it is there
+        already, or the matrix holds a C-ordered dense block of more than 64 columns (wide_dense) whose sparse x dense
+        term builds it anyway -- no slab-form twin is then built for the block at all.  Else None: the slab form."""
+        return self._ent() if (self._entblk is not None or wide_dense) else None
+
+    def _dense_twin(self, width: int, aligned: bool = True, ent_ok: bool = True) -> str:
+        """The twin ladder of the full-pass sparse x dense kernels for an operand of `width` columns ("ent", "lg",
+        "ell", "ellw" or "slab"); each twin is built when it is asked for and may refuse the block.  aligned: the
+        operand is C-ordered with 16-byte rows (ext.sparse.ell_supported), which all but the slab form need."""
+        wide = width > 64
+        if wide and aligned and ent_ok and self._ent() is not None:
+            return "ent"
+        if wide and aligned and self._lg() is not None:
+            return "lg"
+        if aligned and self._ell(wide=wide) is not None:
+            return "ellw" if wide else "ell"
+        return "slab"
+
+    def _dense_kernel(self, width: int, aligned: bool = True, n_rows=None) -> str:
+        """Which kernel the sparse x dense term with an operand of `width` columns runs on -- the only place that
+        knows: "rows" (a short row list of n_rows rows on the chunk-major twin, cost ~ len(rows)), "generic" (nothing
+        to do, or a row list over a block that holds inf / nan), "sorted" (a few nonzeros per row in a wide block:
+        column by column on the CSC form), else one full pass on a twin of _dense_twin, a row list being a masked d
+        (excluded rows contribute exactly 0).  to_device asks with a width alone, _cross_sandwich_dev with what
+        the operand and the call are."""
+        n, m = self.shape
+        nnz = int(self._dev().data.numel())
+        if n_rows is not None and 0 < n_rows <= ROW_LIST_FRACTION_K3 * n and 0 < nnz < 2**31 and m <= 128 * 32:
+            return "rows"
+        if n == 0 or nnz == 0 or (n_rows is not None and not self._values_finite()):
+            return "generic"
+        if nnz <= SORTED_K3_NNZ_PER_ROW * n and m >= 1024 and aligned:
+            return "sorted"
+        return self._dense_twin(width, aligned)
 
     def to_device(self, dense_width=None):
         """Upload and build the twins now (otherwise the first product does it).  dense_width:
@@ -176,16 +224,13 @@ class SparseMatrix(MatrixBase):
             # the self sandwich's static block list: built here, not inside the first product (its builder reads
             # per-tile counts back to the host)
             self._dev().pair_blocks()
-        ent = None
-        if dense_width is not None and dense_width > 0:
-            # (the entry twin only when the sparse x dense term will run on it: not for a few nonzeros per row in a
-            # wide block, which takes the column-sorted kernel -- same test as _cross_sandwich_dev)
-            sorted_k3 = (self._dev().data.numel() <= SORTED_K3_NNZ_PER_ROW * self.shape[0]
-                         and self.shape[1] >= 1024)
-            ent = self._ent() if dense_width > 64 and not sorted_k3 else None
-            if dense_width <= 64 or (ent is None and self._lg() is None):
-                self._ell(wide=dense_width > 64)
-        if ent is None:
+        # (asking builds the twin the sparse x dense term will run on, for a C-ordered operand with 16-byte rows)
+        kernel = self._dense_kernel(dense_width) if dense_width is not None and dense_width > 0 else None
+        if kernel == "sorted":
+            # (the column-sorted kernel reads the CSC form; the ladder below the entry twin is built all the same,
+            # as it always has been for such a block)
+            self._dense_twin(dense_width, ent_ok=False)
+        if kernel != "ent":
             self._slab()       # (categorical x sparse runs on the entry twin when there is one)
         # the twins are built: from here on the hot kernels read them, the 16-bit column twin (unrestricted matvec /
         # transpose_matvec) or nothing of the CSR columns at all -- the int32 column array goes (ext/_types.py)
@@ -267,19 +312,22 @@ class SparseMatrix(MatrixBase):
     def _row_parts(self):
         """None, or [(r0, r1, SparseMatrix)] row slices with fewer than PART_NNZ nonzeros each (the
         twins index entries with 32 bits)."""
-        parts = self.__dict__.get("_parts_cache", False)
-        if parts is False:
-            parts = None
+        def build():
             ptr = self._dev().indptr
             nnz = int(self._dev().data.numel())
-            if nnz >= PART_NNZ:
-                n = self.shape[0]
-                k = -(-nnz // max(1, int(0.8 * PART_NNZ)))
-                targets = torch.arange(1, k, device=ptr.device, dtype=torch.int64) * nnz // k
-                cuts = sorted(set([0] + torch.searchsorted(ptr, targets).clamp_(0, n).tolist() + [n]))
-                parts = [(a, b, self[a:b]) for a, b in zip(cuts[:-1], cuts[1:]) if b > a]
-            self.__dict__["_parts_cache"] = parts
-        return parts
+            if nnz < PART_NNZ:
+                return None
+            n = self.shape[0]
+            k = -(-nnz // max(1, int(0.8 * PART_NNZ)))
+            targets = torch.arange(1, k, device=ptr.device, dtype=torch.int64) * nnz // k
+            cuts = sorted(set([0] + torch.searchsorted(ptr, targets).clamp_(0, n).tolist() + [n]))
+            return [(a, b, self[a:b]) for a, b in zip(cuts[:-1], cuts[1:]) if b > a]
+
+        return self._once("_parts_cache", build)
+
+    def _pays(self, kernel: str) -> bool:
+        """The verdict of ext.sparse.{pairs,direct,blocks}_sandwich_pays on this block (host cost models), asked once."""
+        return self._once("_pays_" + kernel, lambda: getattr(xs, kernel + "_sandwich_pays")(self._dev()))
 
     def _narrow_pays(self, w: int) -> bool:
         """Host cost model (fitted on scripts/dev/time_sparse_cols.py, MI355X): the dense-block form
@@ -291,33 +339,60 @@ class SparseMatrix(MatrixBase):
         pairs = n * per_row * (per_row + 1) / 2
         nch = -(-mcols // 128)
         t_full = max(31e-12 * (nch * (nch + 1) / 2) * n, 1.6e-12 * pairs)
-        if getattr(self, "_direct_pays", None):
+        if self._pays("direct"):
             t_full = pairs / 22e9
         t_narrow = 0.2e-3 + n * w * 4.5e-12 + nnz * w / max(mcols, 1) * 40e-12
         return t_narrow < 0.8 * t_full
 
-    def _sandwich_dev(self, d, rows, cols):
-        parts = self._row_parts()
-        if parts is not None:
-            out = None
-            for a, b, part in parts:
-                r = None
-                if rows is not None:
-                    r64 = rows.to(torch.int64)
-                    sel = r64[(r64 >= a) & (r64 < b)]
-                    if sel.numel() == 0:
-                        continue
-                    r = (sel - a).to(torch.int32)
-                res = part._sandwich_dev(d[a:b], r, cols)
-                out = res if out is None else out + res
-            if out is None:
-                k = self.shape[1] if cols is None else D.nlen(cols)
-                out = D.zeros((k, k), d.dtype)
-            return out
-        A = self._dev()
+    def _sandwich_route(self, n_rows=None, n_cols=None, deterministic=None) -> str:
+        """Which way sandwich(d, rows, cols) goes, from host scalars alone (the shape, the nonzero count, the cost
+        models' cached verdicts, the module constants; free memory through D.free_bytes).  n_rows / n_cols: how
+        many rows / columns are selected, None = all.  deterministic: categorical_matrix.DETERMINISTIC unless given.
+          "parts"          PART_NNZ nonzeros or more: the sum over row parts, each routed on its own
+          "deterministic"  fixed summation order on the entry twin (_sandwich_deterministic)
+          "narrow"         a narrow column selection (a solver's active set): the selected columns written out as
+                           one row-major dense block from the CSC form (only their entries are read), then the
+                           MFMA syrk -- cost in proportion to the selection (ext/sparse.pyx:17-77 with `cols`)
+          "pairs"          wide block: the pair-stream kernel (cost follows the entries and pairs of a row,
+                           csrc/sparse_pairs.hip); not for a short row list, which goes on down this list
+          "direct"         wide and very sparse: cost per pair instead of per (row, tile)
+          "rows"           short row list: the chunk-major pipeline over the selected rows only
+          "blocks", "chunked"  the unrestricted chunk-pointer kernels, on the static block list when it pays
+          "generic"        tm_sparse_sandwich_*, which takes rows and cols itself: more than 32 column chunks, no entry
+        From "pairs" to "chunked" (but "rows") a row restriction is a masked d (the kernels never touch the entries
+        of a row with d == 0; ext/sparse.pyx:46-48: a row mask) and a column restriction selects from the result."""
         from . import categorical_matrix as _cm
 
-        if _cm.DETERMINISTIC and A.data.numel() > 0 and self.shape[0] > 0:
+        n, m = self.shape
+        nnz = int(self._dev().data.numel())
+        if self._row_parts() is not None:
+            return "parts"
+        if (_cm.DETERMINISTIC if deterministic is None else deterministic) and nnz > 0 and n > 0:
+            return "deterministic"
+        w = n_cols or 0
+        if (0 < w <= NARROW_COLS and 2 * w < m and n > 0 and nnz > 0 and self._narrow_pays(w)
+                and n * w * self.dtype.itemsize * 4 < D.free_bytes()):
+            return "narrow"
+        if self._pays("pairs") and (n_rows is None or n_rows > 0.3 * n):
+            return "pairs"
+        if self._pays("direct"):
+            return "direct"
+        if 0 < nnz < 2**31 and m <= 128 * 32:
+            if n_rows is not None and 0 < n_rows <= ROW_LIST_FRACTION * n:
+                return "rows"
+            return "blocks" if self._pays("blocks") else "chunked"
+        return "generic"
+
+    def _sandwich_dev(self, d, rows, cols):
+        n_rows, n_cols = (None if x is None else D.nlen(x) for x in (rows, cols))
+        route = self._sandwich_route(n_rows, n_cols)
+        if route == "parts":
+            out = None
+            for a, b, part, r in _parts_with_rows(self._row_parts(), rows):
+                res = part._sandwich_dev(d[a:b], r, cols)
+                out = res if out is None else out + res
+            return out if out is not None else D.zeros((self.shape[1] if cols is None else n_cols,) * 2, d.dtype)
+        if route == "deterministic":
             res = self._sandwich_deterministic(d, rows, cols)
             if res is not None:
                 return res
@@ -327,86 +402,39 @@ class SparseMatrix(MatrixBase):
             warnings.warn("TABMAT_AMD_DETERMINISTIC=1: this sparse block has no entry twin, its self sandwich "
                           "falls back to the LDS-atomic kernels and is NOT bit-reproducible from run to run",
                           RuntimeWarning, stacklevel=3)
-        if getattr(self, "_direct_pays", None) is None:
-            self._direct_pays = xs.direct_sandwich_pays(A)
-        w = D.nlen(cols) if cols is not None else 0
-        if (0 < w <= NARROW_COLS and 2 * w < self.shape[1] and self.shape[0] > 0 and A.data.numel() > 0
-                and self._narrow_pays(w)
-                and self.shape[0] * w * A.data.element_size() * 4 < torch.cuda.mem_get_info()[0]):
-            # a narrow column selection (a solver's active set): the selected columns written out
-            # as one row-major dense block from the CSC form (only their entries are read), then
-            # the MFMA syrk -- cost in proportion to the selection (ext/sparse.pyx:17-77 with `cols`)
-            from .ext import dense as xd
-            from .ext._types import DenseDev
+            route = self._sandwich_route(n_rows, n_cols, deterministic=False)
+        A = self._dev()
+        if route == "narrow":
+            return self._sandwich_narrow(d, rows, cols)
+        if route == "generic":
+            return xs.sparse_sandwich(A, d, rows, cols)
+        if route == "rows":
+            res = xs.sparse_sandwich_rows(A, d, rows)
+        else:
+            full = {"pairs": xs.sparse_sandwich_pairs, "direct": xs.sparse_sandwich_direct,
+                    "blocks": xs.sparse_sandwich_blocks, "chunked": xs.sparse_sandwich_chunked}[route]
+            res = full(A, D.masked_d(d, rows, as_set=True))
+        return _select(res, cols, cols).contiguous()
 
-            rws, vls, bstart, _, col_bptr = A.csc_blocks()
-            mx = getattr(self, "_max_col_len", None)
-            if mx is None:
-                ends = bstart[col_bptr]
-                mx = self._max_col_len = int((ends[1:] - ends[:-1]).max().item())
-            cd = cols.to(torch.int64)
-            seg = torch.stack([bstart[col_bptr[cd]], bstart[col_bptr[cd + 1]]], dim=1).contiguous()
-            T = torch.zeros((self.shape[0], w), dtype=A.data.dtype, device=A.data.device)
-            xs.csc_densify_cols(rws, vls, seg, torch.arange(w, dtype=torch.int32, device=A.data.device),
-                                mx, T)
-            return xd.dense_sandwich(DenseDev(T, self.shape[0], w, 0), d, rows, None)
-        pp = getattr(self, "_pairs_pay", None)
-        if pp is None:
-            pp = self._pairs_pay = xs.pairs_sandwich_pays(A)
-        if pp and (rows is None or D.nlen(rows) > 0.3 * self.shape[0]):
-            # wide block: the pair-stream kernel (cost follows the entries and pairs of a row, csrc/sparse_pairs.hip);
-            # a long row list is a masked d (the kernel never touches the entries of a row with d == 0); short
-            # ones keep the row-list kernels below
-            d = D.masked_d(d, rows, as_set=True)    # (ext/sparse.pyx:46-48: a row mask)
-            res = xs.sparse_sandwich_pairs(A, d)
-            if cols is not None:
-                c64 = cols.to(torch.int64)
-                res = res[c64][:, c64].contiguous()
-            return res
-        pays = getattr(self, "_direct_pays", None)
-        if pays is None:
-            pays = self._direct_pays = xs.direct_sandwich_pays(A)
-        if pays:
-            # wide and very sparse: cost per pair instead of per (row, tile)
-            d = D.masked_d(d, rows, as_set=True)    # (ext/sparse.pyx:46-48: a row mask)
-            res = xs.sparse_sandwich_direct(A, d)
-            if cols is not None:
-                c64 = cols.to(torch.int64)
-                res = res[c64][:, c64].contiguous()
-            return res
-        if A.data.numel() > 0 and A.data.numel() < 2**31 and self.shape[1] <= 128 * 32:
-            if rows is not None and 0 < D.nlen(rows) <= ROW_LIST_FRACTION * self.shape[0]:
-                # short row list: the same pipeline over the selected rows only
-                res = xs.sparse_sandwich_rows(A, d, rows)
-                if cols is not None:
-                    c64 = cols.to(torch.int64)
-                    res = res[c64][:, c64].contiguous()
-                return res
-            # fast path: unrestricted chunk-pointer kernel; row restriction = masked d,
-            # column restriction = sub-selection of the small result
-            d = D.masked_d(d, rows, as_set=True)    # (ext/sparse.pyx:46-48: a row mask)
-            bl = getattr(self, "_blocks_pay", None)
-            if bl is None:
-                bl = self._blocks_pay = xs.blocks_sandwich_pays(A)
-            res = xs.sparse_sandwich_blocks(A, d) if bl else xs.sparse_sandwich_chunked(A, d)
-            if cols is not None:
-                c64 = cols.to(torch.int64)
-                res = res[c64][:, c64].contiguous()
-            return res
-        return xs.sparse_sandwich(A, d, rows, cols)
+    def _sandwich_narrow(self, d, rows, cols):
+        """The "narrow" route of _sandwich_route."""
+        from .ext import dense as xd
+        from .ext._types import DenseDev
 
-    def _ent_det(self):
-        """The entry twin for the deterministic mode: the one the products use, else (a block so sparse that the
-        padded stream exceeds ELL_MAX_PAD x its nonzeros) one built without that limit -- reproducibility was
-        asked for, the padding is its price."""
-        ent = self._ent()
-        if ent is None:
-            hit = getattr(self, "_entblk_det", None)
-            if hit is None:
-                twin = SlabEnt.from_csr(self._dev(), max_pad=None)
-                hit = self._entblk_det = twin if twin is not None else False
-            ent = hit or None
-        return ent
+        A = self._dev()
+        n, w = self.shape[0], D.nlen(cols)
+        rws, vls, bstart, _, col_bptr = A.csc_blocks()
+
+        def longest_column():
+            ends = bstart[col_bptr]
+            return int((ends[1:] - ends[:-1]).max().item())
+
+        cd = cols.to(torch.int64)
+        seg = torch.stack([bstart[col_bptr[cd]], bstart[col_bptr[cd + 1]]], dim=1).contiguous()
+        T = torch.zeros((n, w), dtype=A.data.dtype, device=A.data.device)
+        xs.csc_densify_cols(rws, vls, seg, torch.arange(w, dtype=torch.int32, device=A.data.device),
+                            self._once("_max_col_len", longest_column), T)
+        return xd.dense_sandwich(DenseDev(T, n, w, 0), d, rows, None)
 
     def _sandwich_deterministic(self, d, rows, cols=None):
         """TABMAT_AMD_DETERMINISTIC=1: the sparse self sandwich with a FIXED summation order, bit-identical
@@ -466,14 +494,7 @@ class SparseMatrix(MatrixBase):
         if parts is not None:
             s1 = D.zeros((self.shape[1],), d.dtype) if want_s1 else None
             s2 = D.zeros((self.shape[1],), d.dtype)
-            for a, b, part in parts:
-                r = None
-                if rows is not None:
-                    r64 = rows.to(torch.int64)
-                    sel = r64[(r64 >= a) & (r64 < b)]
-                    if sel.numel() == 0:
-                        continue
-                    r = (sel - a).to(torch.int32)
+            for a, b, part, r in _parts_with_rows(parts, rows):
                 p1, p2 = part._sdiag_dev(d[a:b], r, want_s1)
                 s2 += p2
                 if want_s1:
@@ -510,8 +531,9 @@ class SparseMatrix(MatrixBase):
         return res if on_dev else D.to_host(res)
 
     def _cross_sandwich_dev(self, other, d, rows, L_cols, R_cols, colsum_box=None):
-        """colsum_box: a list that receives self[rows, L_cols]' d[rows] when the kernel that runs
-        produces it in the same pass (the lane-group K3; SplitMatrix._sandwich_xtd_dev)."""
+        """colsum_box: a list that receives self[rows, L_cols]' d[rows] when the kernel that runs produces it in
+        the same pass (the entry-twin and lane-group K3; SplitMatrix._sandwich_xtd_dev).  The kernel: _dense_kernel;
+        column restrictions select from the small result."""
         from .categorical_matrix import CategoricalMatrix
         from .dense_matrix import DenseMatrix
 
@@ -523,55 +545,27 @@ class SparseMatrix(MatrixBase):
                     f"{other.dtype}.")
             Bd = other._dev_c()
             A = self._dev()
-            if (rows is not None and 0 < D.nlen(rows) <= ROW_LIST_FRACTION_K3 * self.shape[0]
-                    and 0 < A.data.numel() < 2**31 and self.shape[1] <= 128 * 32):
-                # short row list: row-list kernel on the chunk-major twin (cost ~ len(rows))
+            kernel = self._dense_kernel(Bd.m, xs.ell_supported(Bd), None if rows is None else D.nlen(rows))
+            if kernel == "generic":
+                return xs.csr_dense_sandwich(A, Bd, d, rows, L_cols, R_cols)
+            if kernel == "rows":
                 res = xs.csr_dense_sandwich_rows(A, Bd, d, rows)
-                if L_cols is not None:
-                    res = res[L_cols.to(torch.int64)]
-                if R_cols is not None:
-                    res = res[:, R_cols.to(torch.int64)]
-                return res
-            if self.shape[0] > 0 and self._dev().data.numel() > 0 and (
-                    rows is None or self._values_finite()):
-                # fast path: unrestricted slab kernel; a row restriction is a masked d (excluded
-                # rows contribute exactly 0), column restrictions select from the small result
+            else:
                 d = D.masked_d(d, rows)
-                if (A.data.numel() <= SORTED_K3_NNZ_PER_ROW * self.shape[0] and self.shape[1] >= 1024
-                        and xs.ell_supported(Bd)):      # (to_device applies the same test before building twins)
-                    # a few nonzeros per row in a wide block: column by column on the CSC form
+                if kernel == "sorted":
                     res = xs.csc_dense_sandwich_sorted(A, Bd, d)
-                    if L_cols is not None:
-                        res = res[L_cols.to(torch.int64)]
-                    if R_cols is not None:
-                        res = res[:, R_cols.to(torch.int64)]
-                    return res
-                wide = Bd.m > 64 and xs.ell_supported(Bd)
-                ent = self._ent() if wide else None
-                lg = self._lg() if (wide and ent is None) else None
-                ell = None
-                if ent is None and lg is None and xs.ell_supported(Bd):
-                    ell = self._ell(wide=Bd.m > 64)
-                if ent is not None and colsum_box is not None:
-                    res, cs = xs.csr_dense_sandwich_ent(ent, Bd, d, want_colsum=True)
-                    colsum_box.append(cs if L_cols is None else cs[L_cols.to(torch.int64)])
-                elif ent is not None:
-                    res = xs.csr_dense_sandwich_ent(ent, Bd, d)
-                elif lg is not None and colsum_box is not None:
-                    res, cs = xs.csr_dense_sandwich_lg(lg, Bd, d, want_colsum=True)
-                    colsum_box.append(cs if L_cols is None else cs[L_cols.to(torch.int64)])
-                elif lg is not None:
-                    res = xs.csr_dense_sandwich_lg(lg, Bd, d)
-                elif ell is not None:
-                    res = xs.csr_dense_sandwich_ell(ell, Bd, d)
+                elif kernel in ("ent", "lg"):
+                    res = (xs.csr_dense_sandwich_ent(self._ent(), Bd, d, want_colsum=colsum_box is not None)
+                           if kernel == "ent" else
+                           xs.csr_dense_sandwich_lg(self._lg(), Bd, d, want_colsum=colsum_box is not None))
+                    if colsum_box is not None:
+                        res, cs = res
+                        colsum_box.append(_select(cs, L_cols, None))
+                elif kernel in ("ell", "ellw"):
+                    res = xs.csr_dense_sandwich_ell(self._ell(wide=kernel == "ellw"), Bd, d)
                 else:
                     res = xs.csr_dense_sandwich_slab(self._slab(), Bd, d)
-                if L_cols is not None:
-                    res = res[L_cols.to(torch.int64)]
-                if R_cols is not None:
-                    res = res[:, R_cols.to(torch.int64)]
-                return res
-            return xs.csr_dense_sandwich(self._dev(), Bd, d, rows, L_cols, R_cols)
+            return _select(res, L_cols, R_cols)
         if isinstance(other, CategoricalMatrix):
             return other._cross_sandwich_dev(self, d, rows, R_cols, L_cols).T
         raise TypeError

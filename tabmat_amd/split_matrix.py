@@ -21,7 +21,7 @@ from .dense_matrix import DenseMatrix, _centre_and_shift
 from .ext import split as xsplit
 from .ext.dense import dense_glm_loss_grad as xd_glm
 from .ext.dense import dense_sandwich_matvec as xd_smv
-from .matrix_base import MatrixBase
+from .matrix_base import MatrixBase, _parts_with_rows
 from .sparse_matrix import SparseMatrix
 from .standardized_mat import StandardizedMatrix
 from .util import (
@@ -115,19 +115,6 @@ def _zeros_outside(v, cd):
     vm = torch.zeros_like(v)
     vm[cd] = v[cd]
     return vm
-
-
-def _row_parts(parts, rows):
-    """(a, b, part, rows rebased to the part or None) per row part, without the parts a row list leaves empty."""
-    for a, b, part in parts:
-        r = None
-        if rows is not None:
-            r64 = rows.to(torch.int64)
-            sel = r64[(r64 >= a) & (r64 < b)]
-            if sel.numel() == 0:
-                continue
-            r = (sel - a).to(torch.int32)
-        yield a, b, part, r
 
 
 class _Assembly:
@@ -456,14 +443,6 @@ class SplitMatrix(MatrixBase):
             return self.indices, [None] * len(self.indices), self.shape[1]
         return xsplit.split_col_subsets(self, set_up_rows_or_cols(cols, self.shape[1]))
 
-    def _once(self, name, build, cat_ids=()):
-        """build() the first time (per set of categorical blocks, if it is for one); the same value ever after."""
-        cache = self.__dict__.setdefault(name, {})
-        key = tuple(cat_ids)
-        if key not in cache:
-            cache[key] = build()
-        return cache[key]
-
     def _for_cols(self, name, cols_host, build):
         """build() for the LAST column selection (a solver repeats its active set): a new one replaces the old."""
         key = np.asarray(cols_host).tobytes()
@@ -732,11 +711,8 @@ class SplitMatrix(MatrixBase):
                 and mw._dev().data.numel() > 0 and (rows is None or mw._values_finite())):
             # on the entry twin when the sparse x dense term of this matrix runs on it anyway (a C-ordered dense
             # block of more than 64 columns): no slab-form twin is built for the block at all
-            ent = None
-            if len(cats) <= 8 and (getattr(mw, "_entblk", None) or any(
-                    isinstance(mo, DenseMatrix) and mo.shape[1] > 64 and mo.dtype == mw.dtype
-                    for mo in self.matrices)):
-                ent = mw._ent()
+            ent = mw._ent_for_cats(any(isinstance(mo, DenseMatrix) and mo.shape[1] > 64 and mo.dtype == mw.dtype
+                                       for mo in self.matrices)) if len(cats) <= 8 else None
             if ent is not None:
                 # (static per set of categoricals: one word of tile rows per row)
                 packed = self._once("_packed_codes", lambda: xsplit.pack_codes(cats), cat_ids)
@@ -775,7 +751,7 @@ class SplitMatrix(MatrixBase):
         """Sum of the parts' sandwiches (and of their column sums; with `center` the column sums of the centred
         blocks are handed on RAW: a part's centred sum + centre * the part's sum of weights)."""
         out = None
-        for a, b, part, r in _row_parts(parts, rows):
+        for a, b, part, r in _parts_with_rows(parts, rows):
             cs = [None] * len(self.matrices) if colsum is not None else None
             sub_cen = None if center is None else _Centering(center.vec)
             res = part._sandwich_dev(d[a:b], r, cols_host, None, cs, center=sub_cen)
@@ -1095,7 +1071,7 @@ class SplitMatrix(MatrixBase):
         s2 = D.zeros((p,), torch.float64)
         s1 = D.zeros((p,), torch.float64) if want_s1 else None
         if parts is not None:
-            for a, b, part, r in _row_parts(parts, rows):
+            for a, b, part, r in _parts_with_rows(parts, rows):
                 p2, p1 = part._sdiag_dev(d[a:b], r, cols_host, centers, want_s1)
                 s2 += p2
                 if want_s1:

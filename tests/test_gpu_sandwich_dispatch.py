@@ -396,9 +396,9 @@ for _seed in range(8):
     CASES[f"fuzz_{_seed}"] = (lambda t, _s=_seed: _fuzz(t, _s))
 
 
-def record(case, mp):
+def record(case, mp, cases=CASES):
     t = Tracer(mp)
-    CASES[case](t)
+    cases[case](t)
     return t.calls
 
 
@@ -409,15 +409,14 @@ def _encode(seq, dropped):
 
 
 # ---- the test --------------------------------------------------------------------------------------------------
-_golden = None
+_golden = {}
 
 
-def _load():
-    global _golden
-    if _golden is None:
-        with open(GOLDEN) as f:
-            _golden = json.load(f)
-    return _golden
+def _load(path=GOLDEN):
+    if path not in _golden:
+        with open(path) as f:
+            _golden[path] = json.load(f)
+    return _golden[path]
 
 
 # one test per group of cases (a case is one design; the golden file is keyed by case)
@@ -428,11 +427,12 @@ GROUPS = {"mixed": ["mixed_f64", "mixed_f32"],
 assert sorted(c for g in GROUPS.values() for c in g) == sorted(CASES)
 
 
-def _check_case(case, mp):
-    gold = _load()
+def _check_case(case, mp, cases=CASES, golden=GOLDEN):
+    """(cases / golden: another module's case table and golden file -- tests/test_gpu_sparse_dispatch.py)"""
+    gold = _load(golden)
     assert case in gold["cases"], f"{case} is not in the golden file (dropped there as data-dependent?)"
     want = gold["cases"][case]
-    got = record(case, mp)
+    got = record(case, mp, cases)
     assert list(got) == list(want), case
     for label, seqs in got.items():
         for k, seq in enumerate(seqs):
@@ -450,30 +450,30 @@ def test_sandwich_dispatch(group, monkeypatch):
 
 
 # ---- the recorder ----------------------------------------------------------------------------------------------
-def _record_all():
+def _record_all(cases=CASES):
     out = {}
-    for case in CASES:
+    for case in cases:
         mp = pytest.MonkeyPatch()
         try:
-            out[case] = record(case, mp)
+            out[case] = record(case, mp, cases)
         finally:
             mp.undo()
         print(f"recorded {case}: {sum(len(s) for v in out[case].values() for s in v)} launches", flush=True)
     return out
 
 
-def main(argv):
+def main(argv, cases=CASES, golden=GOLDEN):
     import argparse
     import subprocess
 
     ap = argparse.ArgumentParser()
     ap.add_argument("--commit", help="hash of the commit this is recorded on (default: git rev-parse HEAD)")
-    ap.add_argument("--out", default=GOLDEN)
+    ap.add_argument("--out", default=golden)
     a = ap.parse_args(argv)
     commit = a.commit or subprocess.check_output(["git", "rev-parse", "HEAD"], cwd=HERE, text=True).strip()
-    first, second = _record_all(), _record_all()
+    first, second = _record_all(cases), _record_all(cases)
     dropped, unstable = {}, []
-    for case in CASES:
+    for case in cases:
         names = [[[n for n, _ in s] for s in seqs] for seqs in first[case].values()]
         if names != [[[n for n, _ in s] for s in seqs] for seqs in second[case].values()]:
             unstable.append(case)
@@ -485,17 +485,17 @@ def main(argv):
                         if xa[k] != xb[k]:
                             dropped.setdefault(name, set()).add(k)
     dropped = {k: sorted(v) for k, v in sorted(dropped.items())}
-    table, cases = {}, {}
-    for case in CASES:
+    table, recorded = {}, {}
+    for case in cases:
         if case in unstable:
             continue
-        cases[case] = {label: [[table.setdefault(s, len(table)) for s in _encode(seq, dropped)] for seq in seqs]
+        recorded[case] = {label: [[table.setdefault(s, len(table)) for s in _encode(seq, dropped)] for seq in seqs]
                        for label, seqs in first[case].items()}
     lines = ["{", f' "parent": {json.dumps(commit)},', f' "dropped": {json.dumps(dropped)},', ' "launches": [']
     lines += [f"  {json.dumps(s)}," for s in table]
     lines[-1] = lines[-1][:-1]
     lines += [" ],", ' "cases": {']
-    for case, labels in cases.items():
+    for case, labels in recorded.items():
         lines.append(f"  {json.dumps(case)}: {{")
         lines += [f"   {json.dumps(label)}: {json.dumps(seqs, separators=(',', ':'))}," for label, seqs in labels.items()]
         if labels:
