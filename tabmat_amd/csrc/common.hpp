@@ -15,6 +15,8 @@ constexpr int NUM_CU = 256;        // MI355X
 constexpr int NUM_XCD = 8;
 constexpr int SPARSE_CHUNK_COLS = 128;   // columns per chunk of the chunk-major CSR twin (tm_sparse_chunk_cols)
 constexpr size_t LDS_BYTES = 160 * 1024;
+// the largest LDS tile of the categorical kernels (cat.hip, cat_multi.hip): a tile alone, one workgroup per CU
+constexpr size_t HIST_LDS_MAX = 128 * 1024;
 
 void set_error(const char *fmt, ...);
 int hip_fail(hipError_t e, const char *what, const char *file, int line);

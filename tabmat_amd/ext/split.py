@@ -381,7 +381,7 @@ def _cat_args(cats):
 
 
 def multi_cat_dense_wide_ok(cats, mat_j: DenseDev) -> bool:
-    """True when tm_multi_cat_dense_sandwich_* takes its wide-load LDS-atomic kernel (cat.hip,
+    """True when tm_multi_cat_dense_sandwich_* takes its wide-load LDS-atomic kernel (cat_multi.hip,
     multi_cat_dense_wide_kernel): C-ordered operand with 16-byte aligned rows, <= 8 categoricals,
     stacked tile of DOUBLES [sum(n_cols)][32] plus the per-wave scratch within 150 KB of LDS."""
     fb = mat_j.buf.element_size()
@@ -403,7 +403,7 @@ def multi_cat_dense_tile_ok(cats, mat_j: DenseDev) -> bool:
     if total == 0 or m == 0 or not 1 <= len(cats) <= 16:
         return False
     tj = 64
-    while tj > 1 and 8 * total * tj > 128 * 1024:        # HIST_LDS_MAX of csrc/cat.hip
+    while tj > 1 and 8 * total * tj > 128 * 1024:        # HIST_LDS_MAX of csrc/common.hpp
         tj >>= 1
     while tj > 1 and tj // 2 >= m:
         tj >>= 1

@@ -8,7 +8,7 @@ in steps of 64 slots (lane <-> slot), aligned to the first batch of the range, a
     cur_slab = the slab lane 63 got                    for the NEXT step;  cur_slab = s0 before the first
 
 -- `expand` in csr_dense_ent_kernel (csrc/sparse_ent.hip, "auto expand = [&](unsigned m16)") and `load_rows` in
-multi_cat_sparse_ent_kernel (csrc/cat.hip, "auto load_rows = [&](Step &t)": EN_CS_U chained 64-slot sub-steps per call,
+multi_cat_sparse_ent_kernel (csrc/cat_multi.hip, "auto load_rows = [&](Step &t)": EN_CS_U chained 64-slot sub-steps per call,
 which is the same chain).  Lanes past the end of the range: K3 reads whatever follows in the stream (the next group's
 batches or the zero slack), the gather kernel reads the range's last slot (`load_stream`: `e1 - 1`)."""
 import numpy as np
@@ -96,7 +96,7 @@ def wrong_real_slots(st, group, s0, s1, tail):
 
 
 def block_ranges(n_slabs, nblk):
-    """The launchers' cut of the slabs into workgroup ranges (csrc/sparse_ent.hip run_csr_dense_ent, csrc/cat.hip
+    """The launchers' cut of the slabs into workgroup ranges (csrc/sparse_ent.hip run_csr_dense_ent, csrc/cat_multi.hip
     run_multi_cat_sparse_ent: nblk = min(nblk, slabs); spb = ceil(slabs / nblk); ranges of spb slabs)."""
     if n_slabs == 0:
         return []
@@ -106,7 +106,7 @@ def block_ranges(n_slabs, nblk):
 
 
 def wave_ranges(s0, s1, nwh):
-    """The gather kernel's cut of a workgroup's range among the nwh waves of a group (`spw`, csrc/cat.hip
+    """The gather kernel's cut of a workgroup's range among the nwh waves of a group (`spw`, csrc/cat_multi.hip
     multi_cat_sparse_ent_kernel)."""
     spw = -(-(s1 - s0) // nwh)
     out = []

@@ -1,5 +1,5 @@
 """The entry twin's slab decode over LONG row ranges (tabmat_amd/ext/_types.py::SlabEnt; csrc/sparse_ent.hip `expand`,
-csrc/cat.hip `load_rows`).
+csrc/cat_multi.hip `load_rows`).
 
 A slot carries `slab & 63`; the kernels rebuild the slab of all 64 slots of a step against ONE running slab, taken
 over from the step's last slot.  That is right only if the five batches a step sees -- the last one of the step before

@@ -239,7 +239,7 @@ def test_cat_sparse_gather_kernel_10M_long_wave_ranges():
     n_slabs = -(-n // 64)
     n_groups = -(-m // 16)
     n_pairs = (n_groups + 1) // 2
-    blocks = es.block_ranges(n_slabs, es.NUM_CU // n_pairs)           # run_multi_cat_sparse_ent, csrc/cat.hip
+    blocks = es.block_ranges(n_slabs, es.NUM_CU // n_pairs)           # run_multi_cat_sparse_ent, csrc/cat_multi.hip
     waves = [w for s0, s1 in blocks for w in es.wave_ranges(s0, s1, 8)]   # 16 waves, alternating between two groups
     assert len(blocks) == 128 and len(waves) == 1024
     assert max(b - a for a, b in waves) == 153, "the launch rule changed: this design is stale"

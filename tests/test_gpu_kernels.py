@@ -695,7 +695,7 @@ def test_cat_dense(order, ncat, k):
 @pytest.mark.parametrize("n,k,ncats", [(1, 4, (3,)), (31, 32, (5, 2)), (32, 36, (7,)), (33, 128, (256, 96, 32)),
                                        (4097, 132, (11, 3, 2, 9)), (70_000, 8, (300, 40)), (5000, 260, (64,))])
 def test_multi_cat_dense_wide_kernel(dtype, n, k, ncats):
-    """tm_multi_cat_dense_sandwich_* on its wide-load path (cat.hip multi_cat_dense_wide_kernel):
+    """tm_multi_cat_dense_sandwich_* on its wide-load path (cat_multi.hip multi_cat_dense_wide_kernel):
     1..4 categoricals, row counts around the 32-row wave step, column counts that are not multiples
     of the 16 * VEC part width, drop_first, missing codes, rows with d == 0 holding inf."""
     import tabmat_amd as tm

@@ -66,7 +66,7 @@ def test_lg_rounds(lg_rounds, compact, dtype, tune):
 @pytest.mark.parametrize("waves", [4, 16])
 @pytest.mark.parametrize("rounds", ROUNDS)
 def test_catdense_rounds_and_waves(rounds, waves, dtype, tune):
-    """tm_multi_cat_dense_sandwich_* on its wide-load path (csrc/cat.hip multi_cat_dense_wide_kernel);
+    """tm_multi_cat_dense_sandwich_* on its wide-load path (csrc/cat_multi.hip multi_cat_dense_wide_kernel);
     tests/test_gpu_kernels.py test_multi_cat_dense_wide_kernel: cross_err < 1e-10 / 1e-4."""
     import tabmat_amd as tm
     from tabmat_amd import _device as D
@@ -118,7 +118,7 @@ def _cat_sparse_case(dtype, m):
 @pytest.mark.parametrize("waves", [4, 16])
 @pytest.mark.parametrize("rounds", ROUNDS)
 def test_catsparse_rounds_and_waves_slab_form(rounds, waves, dtype, tune):
-    """tm_multi_cat_sparse_sandwich_slab_* (csrc/cat.hip run_multi_cat_sparse); tolerance of
+    """tm_multi_cat_sparse_sandwich_slab_* (csrc/cat_multi.hip run_multi_cat_sparse); tolerance of
     tests/test_gpu_row_list.py test_cat_sparse_row_list_kernel (the same reduction): 1e-10 / 3e-4 of max|ref|."""
     import tabmat_amd as tm
     from tabmat_amd import _device as D
@@ -140,7 +140,7 @@ def test_catsparse_rounds_and_waves_slab_form(rounds, waves, dtype, tune):
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("rounds", ROUNDS)
 def test_catsparse_rounds_row_list_form(rounds, dtype, tune):
-    """tm_multi_cat_sparse_sandwich_rows_* (csrc/cat.hip run_multi_cat_sparse_rows), 12 000 selected rows with repeats;
+    """tm_multi_cat_sparse_sandwich_rows_* (csrc/cat_multi.hip run_multi_cat_sparse_rows), 12 000 selected rows with repeats;
     tests/test_gpu_row_list.py test_cat_sparse_row_list_kernel: 1e-10 / 3e-4 of max|ref|."""
     import tabmat_amd as tm
     from tabmat_amd import _device as D
