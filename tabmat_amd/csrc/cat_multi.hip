@@ -297,7 +297,7 @@ __global__ void multi_cat_untile_kernel(const F *__restrict__ tmp, int64_t total
     out[e] = tmp[((j / TJ) * total + a) * TJ + (j % TJ)];
 }
 
-// Sparse operand in slab-blocked column-major form (sparse.hip): part = one 32-column group,
+// Sparse operand in slab-blocked column-major form (sparse_slab.hip): part = one 32-column group,
 // lane <-> nonzero of the (slab, group) stream.  The LDS tile has a row stride of
 // group_cols + 1: consecutive stream entries belong to the same column (runs of ~6 rows), with an
 // unpadded stride they would all fall on one bank pair.  STAGE: every wave first copies the

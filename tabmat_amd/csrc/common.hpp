@@ -92,6 +92,7 @@ int run_syrk_narrow(const F *X, int64_t n, int64_t m, int order_f, const F *d, F
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }   // pieces of a workspace
 
 // ---------------------------------------------------------------------------------
 // device helpers

@@ -44,6 +44,7 @@
 // physical-register constraints: the index mode needs a base register known when the code is written.
 #include "common.hpp"
 #include "reduce.hpp"
+#include "slab_launch.hpp"
 
 namespace tmh {
 
@@ -449,89 +450,32 @@ __global__ __launch_bounds__(EN_THREADS) __attribute__((amdgpu_num_vgpr(EN_CVGPR
     }
 }
 
-// tmp [part][m][128] -> out[m][nB]
-template <typename F>
-__global__ void en_untile_kernel(const F *__restrict__ tmp, int64_t m, int64_t nB, F *__restrict__ out) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= m * nB) return;
-    const int64_t i = e / nB, j = e % nB;
-    out[e] = tmp[((j / EN_W) * m + i) * EN_W + (j % EN_W)];
-}
-
-// column sums: csum[c] = sum over the workgroups (fixed order) of their partial sums
-template <typename F>
-__global__ void en_csum_kernel(const F *__restrict__ part, int nblk, int64_t m, F *__restrict__ csum) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= m) return;
-    double a = 0.0;
-    for (int b = 0; b < nblk; ++b) a += (double)part[(int64_t)b * m + c];
-    csum[c] = (F)a;
-}
+constexpr SlabGeom EN_GEOM{EN_R, EN_C, EN_NW, EN_W, false};
 
 template <typename F>
 static int run_csr_dense_ent(const F *vals, const uint16_t *meta, const uint32_t *bstart, int64_t n, int64_t m,
                              const F *B, int64_t r, const F *d, F *out, F *colsum, hipStream_t st) {
     const int64_t nB = r;
-    const int64_t total = m * nB;
-    if (total == 0) return TM_OK;
-    constexpr int VEC = 16 / (int)sizeof(F);
-    if ((reinterpret_cast<uintptr_t>(B) & 15) != 0 || r % VEC != 0 || nB < VEC) {
-        set_error("tm_csr_dense_sandwich_ent: B must be C-ordered with 16-byte aligned rows");
-        return TM_EUNSUPPORTED;
-    }
-    if (m % EN_C != 0) {
-        set_error("tm_csr_dense_sandwich_ent: m must be a multiple of tm_ent_group_cols()");
-        return TM_EINVAL;
-    }
+    if (m * nB == 0) return TM_OK;
+    int rc = slab_check_b("tm_csr_dense_sandwich_ent", B, r);
+    if (!rc) rc = slab_check_m("tm_csr_dense_sandwich_ent", m, EN_C);
+    if (rc) return rc;
     if (n >= (1ll << 28)) {      // meta = row << 4 | column
         set_error("tm_csr_dense_sandwich_ent: at most 2^28 - 1 rows per block (work in row parts)");
         return TM_EUNSUPPORTED;
     }
-    const int64_t n_slabs = ceil_div(n, EN_R);
-    const int n_groups = (int)(m / EN_C);
-    const int n_parts = (int)ceil_div(nB, EN_W);
-    const int nz = (int)ceil_div(n_groups, EN_NW);
+    const SlabPlan p = slab_plan(n, m, nB, EN_GEOM, tune("ent_rounds", 1));
+    if (p.n_slabs == 0) return slab_zero_fill(out, m, nB, colsum, st);
     const bool want_csum = colsum != nullptr;
-    if (n_slabs == 0) {
-        TM_HIP(hipMemsetAsync(out, 0, sizeof(F) * (size_t)total, st));
-        if (want_csum) TM_HIP(hipMemsetAsync(colsum, 0, sizeof(F) * (size_t)m, st));
-        return TM_OK;
-    }
-    int64_t nblk = std::max<int64_t>(1, tune("ent_rounds", 1) * NUM_CU / ((int64_t)n_parts * nz));
-    nblk = std::min<int64_t>(nblk, n_slabs);
-    const int64_t spb = ceil_div(n_slabs, nblk);
-    nblk = ceil_div(n_slabs, spb);
-    const int64_t stride = m * EN_W;  // per (part, block)
-    const size_t tmp_bytes = (sizeof(F) * (size_t)(n_parts * stride) + 255) / 256 * 256;
-    const size_t part_bytes = (sizeof(F) * (size_t)((int64_t)n_parts * nblk * stride) + 255) / 256 * 256;
-    const size_t csum_bytes = ((want_csum ? sizeof(F) * (size_t)(nblk * m) : 0) + 255) / 256 * 256 + 256;
-    void *wsv = nullptr;
-    int rc = get_workspace(tmp_bytes + part_bytes + csum_bytes + 256, &wsv, st);
+    SlabWs<F> w;
+    rc = slab_workspace(p, want_csum ? m : 0, 0, st, &w);
     if (rc) return rc;
-    F *tmp = reinterpret_cast<F *>(wsv);
-    F *ws = reinterpret_cast<F *>(reinterpret_cast<char *>(wsv) + tmp_bytes);
-    F *ws_csum = reinterpret_cast<F *>(reinterpret_cast<char *>(wsv) + tmp_bytes + part_bytes);
     const size_t lds = (size_t)EnLds<F>::TOTAL;
     auto kern = want_csum ? &csr_dense_ent_kernel<F, true> : &csr_dense_ent_kernel<F, false>;
-    TM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    prof_begin(st);
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk, (unsigned)n_parts, (unsigned)nz), dim3(EN_THREADS), lds, st,
-                       vals, meta, bstart, n_groups, n_slabs, spb, B, n, r, (int)nB, d, ws, ws_csum,
-                       reinterpret_cast<long long *>((uintptr_t)tune("ent_prof", 0)));
-    prof_end(st);
-    TM_LAUNCH_CHECK();
-    rc = launch_reduce_partials<F>(ws, stride, (int)nblk, n_parts, tmp, n_parts * stride, false, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL((en_untile_kernel<F>), dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st, tmp, m,
-                       nB, out);
-    TM_LAUNCH_CHECK();
-    if (want_csum) {
-        hipLaunchKernelGGL((en_csum_kernel<F>), dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, st, ws_csum,
-                           (int)nblk, m, colsum);
-        TM_LAUNCH_CHECK();
-    }
-    return TM_OK;
+    return slab_launch_and_finish<F>(kern, p, lds, w, m, nB, out, colsum, st, [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(kern, grid, block, lds, st, vals, meta, bstart, p.n_groups, p.n_slabs, p.spb, B, n, r,
+                           (int)nB, d, w.part, w.csum, reinterpret_cast<long long *>((uintptr_t)tune("ent_prof", 0)));
+    });
 }
 
 }  // namespace tmh

@@ -31,6 +31,7 @@
 // pairs behind one scalar bit test.
 #include "common.hpp"
 #include "reduce.hpp"
+#include "slab_launch.hpp"
 
 namespace tmh {
 
@@ -574,78 +575,34 @@ __global__ __launch_bounds__(LG_THREADS / NG) void csr_dense_lg_kernel(
     }
 }
 
-// tmp [part][m][128] -> out[m][nB]
-template <typename F>
-__global__ void lg_untile_kernel(const F *__restrict__ tmp, int64_t m, int64_t nB,
-                                 F *__restrict__ out) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= m * nB) return;
-    const int64_t i = e / nB, j = e % nB;
-    out[e] = tmp[((j / LG_W) * m + i) * LG_W + (j % LG_W)];
-}
-
-// column sums: csum[c] = sum over the workgroups (fixed order) of their partial sums
-template <typename F>
-__global__ void lg_csum_kernel(const F *__restrict__ part, int nblk, int64_t m, F *__restrict__ csum) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= m) return;
-    double a = 0.0;
-    for (int b = 0; b < nblk; ++b) a += (double)part[(int64_t)b * m + c];
-    csum[c] = (F)a;
-}
+constexpr SlabGeom LG_GEOM{LG_R, LG_C, LG_NW, LG_W, false};
 
 template <typename F>
 static int run_csr_dense_lg(const F *vals, const unsigned *koff, const int64_t *xptr, const F *xvals,
                             const unsigned *xkoff, int64_t n, int64_t m, const F *B, int64_t r,
                             const F *d, int unc, F *out, F *colsum, bool compact, hipStream_t st) {
     const int64_t nB = r;
-    const int64_t total = m * nB;
-    if (total == 0) return TM_OK;
-    constexpr int VEC = 16 / (int)sizeof(F);
-    if ((reinterpret_cast<uintptr_t>(B) & 15) != 0 || r % VEC != 0 || nB < VEC) {
-        set_error("tm_csr_dense_sandwich_lg: B must be C-ordered with 16-byte aligned rows");
-        return TM_EUNSUPPORTED;
-    }
-    if (m % LG_C != 0) {
-        set_error("tm_csr_dense_sandwich_lg: m must be a multiple of tm_lg_group_cols()");
-        return TM_EINVAL;
-    }
-    const int64_t n_slabs = ceil_div(n, LG_R);
-    const int n_groups = (int)(m / LG_C);
-    const int n_parts = (int)ceil_div(nB, LG_W);
-    const int nz = (int)ceil_div(n_groups, LG_NW);
+    if (m * nB == 0) return TM_OK;
+    int rc = slab_check_b("tm_csr_dense_sandwich_lg", B, r);
+    if (!rc) rc = slab_check_m("tm_csr_dense_sandwich_lg", m, LG_C);
+    if (rc) return rc;
+    const SlabPlan p = slab_plan(n, m, nB, LG_GEOM, tune("lg_rounds", 1));
+    if (p.n_slabs == 0) return slab_zero_fill(out, m, nB, colsum, st);
     const bool want_csum = colsum != nullptr;
-    if (n_slabs == 0) {
-        TM_HIP(hipMemsetAsync(out, 0, sizeof(F) * (size_t)total, st));
-        if (want_csum) TM_HIP(hipMemsetAsync(colsum, 0, sizeof(F) * (size_t)m, st));
-        return TM_OK;
-    }
-    int64_t nblk = std::max<int64_t>(1, tune("lg_rounds", 1) * NUM_CU / ((int64_t)n_parts * nz));
-    nblk = std::min<int64_t>(nblk, n_slabs);
-    const int64_t spb = ceil_div(n_slabs, nblk);
-    nblk = ceil_div(n_slabs, spb);
-    const int64_t stride = m * LG_W;  // per (part, block)
-    const size_t tmp_bytes = (sizeof(F) * (size_t)(n_parts * stride) + 255) / 256 * 256;
-    const size_t part_bytes = (sizeof(F) * (size_t)((int64_t)n_parts * nblk * stride) + 255) / 256 * 256;
-    const size_t csum_bytes = ((want_csum ? sizeof(F) * (size_t)(nblk * m) : 0) + 255) / 256 * 256 + 256;
     // soft lockstep of the column-half workgroups (21.2 -> 18.1 GB of HBM traffic at cfg4, same
     // time); tm_tune_set("lg_lockstep", 0) switches it off
     const int lockstep = (int)tune("lg_lockstep", 1);
-    const size_t prog_bytes = (sizeof(int) * (size_t)(n_parts * nblk * nz) + 255) / 256 * 256;
-    void *wsv = nullptr;
-    int rc = get_workspace(tmp_bytes + part_bytes + csum_bytes + prog_bytes + 256, &wsv, st);
+    const size_t prog_bytes = align256(sizeof(int) * (size_t)(p.n_parts * p.nblk * p.nz));
+    SlabWs<F> w;
+    rc = slab_workspace(p, want_csum ? m : 0, prog_bytes, st, &w);
     if (rc) return rc;
-    F *tmp = reinterpret_cast<F *>(wsv);
-    F *ws = reinterpret_cast<F *>(reinterpret_cast<char *>(wsv) + tmp_bytes);
-    F *ws_csum = reinterpret_cast<F *>(reinterpret_cast<char *>(wsv) + tmp_bytes + part_bytes);
     int *prog = nullptr;
-    if (lockstep && nz > 1) {
-        prog = reinterpret_cast<int *>(reinterpret_cast<char *>(wsv) + tmp_bytes + part_bytes + csum_bytes);
+    if (lockstep && p.nz > 1) {
+        prog = reinterpret_cast<int *>(w.extra);
         TM_HIP(hipMemsetAsync(prog, 0, prog_bytes, st));
     }
-    const size_t lds = (size_t)LgLds<F>::TOTAL;
     // (groups with no columns at all leave their slots of the partial sums untouched)
-    if (want_csum) TM_HIP(hipMemsetAsync(ws_csum, 0, sizeof(F) * (size_t)(nblk * m), st));
+    if (want_csum) TM_HIP(hipMemsetAsync(w.csum, 0, sizeof(F) * (size_t)(p.nblk * m), st));
     // (f64 with 4 unconditional positions has no registers left for the column sums: UNC = 2 there)
     auto kern = want_csum ? (unc >= 4 && sizeof(F) == 4 ? &csr_dense_lg_kernel<F, 4, 1, true>
                                                         : &csr_dense_lg_kernel<F, 2, 1, true>)
@@ -655,26 +612,11 @@ static int run_csr_dense_lg(const F *vals, const unsigned *koff, const int64_t *
                                                        : &csr_dense_lg_kernel<F, 2, 1, true, true>)
                          : (unc >= 4 ? &csr_dense_lg_kernel<F, 4, 1, false, true>
                                      : &csr_dense_lg_kernel<F, 2, 1, false, true>);
-    const int threads = LG_THREADS;
-    TM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    prof_begin(st);
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk, (unsigned)n_parts, (unsigned)nz), dim3(threads),
-                       lds, st, vals, koff, xptr, xvals, xkoff, n_groups, n_slabs, spb, B, n, r,
-                       (int)nB, d, ws, ws_csum, prog);
-    prof_end(st);
-    TM_LAUNCH_CHECK();
-    rc = launch_reduce_partials<F>(ws, stride, (int)nblk, n_parts, tmp, n_parts * stride, false, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL((lg_untile_kernel<F>), dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st,
-                       tmp, m, nB, out);
-    TM_LAUNCH_CHECK();
-    if (want_csum) {
-        hipLaunchKernelGGL((lg_csum_kernel<F>), dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, st, ws_csum,
-                           (int)nblk, m, colsum);
-        TM_LAUNCH_CHECK();
-    }
-    return TM_OK;
+    const size_t lds = (size_t)LgLds<F>::TOTAL;
+    return slab_launch_and_finish<F>(kern, p, lds, w, m, nB, out, colsum, st, [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(kern, grid, block, lds, st, vals, koff, xptr, xvals, xkoff, p.n_groups, p.n_slabs, p.spb, B,
+                           n, r, (int)nB, d, w.part, w.csum, prog);
+    });
 }
 
 }  // namespace tmh

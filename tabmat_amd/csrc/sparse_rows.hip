@@ -113,7 +113,7 @@ static int run_csr_dense_rows(const F *data, const IX *ind, const int32_t *range
     nblk = ceil_div(n_sel, rpb);
     const int64_t stride = (int64_t)RK_TS * RK_W;
     const int n_parts = nch * nz;
-    const size_t tmp_bytes = (sizeof(F) * (size_t)(n_parts * stride) + 255) / 256 * 256;
+    const size_t tmp_bytes = align256(sizeof(F) * (size_t)(n_parts * stride));
     void *wsv = nullptr;
     int rc = get_workspace(tmp_bytes + sizeof(F) * (size_t)((int64_t)n_parts * nblk * stride) + 256, &wsv, st);
     if (rc) return rc;

@@ -109,7 +109,7 @@ def csr_matvec_multi(X: CsrDev, V, rows, cols, transpose):
 
 def csr_dense_sandwich_slab(A: SlabCsc, B: DenseDev, d):
     """Fast path of ext/sparse.pyx:211-260 for an unrestricted product (B C- or F-ordered):
-    slab-blocked gather kernel with static register accumulators (csrc/sparse.hip, K3)."""
+    slab-blocked gather kernel with static register accumulators (csrc/sparse_slab.hip, K3)."""
     assert B.n == A.n
     out = D.zeros((A.m, B.m), A.vals.dtype)
     if A.m == 0 or B.m == 0 or A.n == 0:
@@ -128,7 +128,7 @@ def ell_supported(B: DenseDev) -> bool:
 
 def csr_dense_sandwich_ell(A: SlabEll, B: DenseDev, d):
     """Fast path of ext/sparse.pyx:211-260 for an unrestricted product with a C-ordered B:
-    interleaved-ELL twin, static iterations with skip masks (csrc/sparse.hip, K3 ELL)."""
+    interleaved-ELL twin, static iterations with skip masks (csrc/sparse_slab.hip, K3 ELL)."""
     assert B.n == A.n and ell_supported(B)
     if A.m == 0 or B.m == 0 or A.n == 0:
         return D.zeros((A.m, B.m), A.vals.dtype)

@@ -1,5 +1,6 @@
 """SparseMatrix: a sorted CSC matrix on the host whose CSR twin is resident in HBM (reference:
-/root/reference/src/tabmat/sparse_matrix.py).  Kernels: tabmat_amd/csrc/sparse.hip."""
+/root/reference/src/tabmat/sparse_matrix.py).  Kernels: tabmat_amd/csrc/sparse.hip; the slab-twin
+sparse x dense kernels (K3): sparse_slab.hip, sparse_lg.hip, sparse_ent.hip."""
 from __future__ import annotations
 
 import os

@@ -695,7 +695,7 @@ class SplitMatrix(MatrixBase):
                 return None          # pair by pair on the level-sorted kernel
             # (F-ordered / unaligned operand) stacked one-hot encodings as a
             # 1-nonzero-per-row-and-categorical sparse block in slab form -> atomic-free gather
-            # kernel (sparse.hip, K3 v2)
+            # kernel (sparse_slab.hip, K3 v2)
             from .ext import sparse as xs
 
             oh, inv = self._onehot_slab(cat_ids)

@@ -297,7 +297,7 @@ def test_csr_dense_sandwich(order, n, m, r):
                                         (63, 1, 260, 0.9), (20000, 40, 66, 0.0)])
 def test_csr_dense_sandwich_wide_ell(dtype, n, m, r, dens):
     """Dense operands with more than 64 columns take the wide interleaved-ELL kernel
-    (tm_csr_dense_sandwich_ellw_*, sparse.hip K3 wide): part widths that are not multiples of 128,
+    (tm_csr_dense_sandwich_ellw_*, sparse_slab.hip K3 wide): part widths that are not multiples of 128,
     more than 256 sparse columns (blockIdx.z), row counts around the 64-row slab, blocks longer than
     the 3 prefetched chunks (dense columns), rows excluded by d == 0, an empty matrix."""
     import tabmat_amd as tm
